@@ -5,6 +5,8 @@ parameter gradients.
 
     python bench.py --gpus N --steps K --warmup W            (N>1: under torch.distributed.run, or bare -- it then starts
                                                               the N ranks itself and refuses to run on fewer GPUs)
+    python bench.py ... --dump-outputs DIR                   (also write the last timed step's results as DIR/*.npy: the
+                                                              inputs are seeded, so two builds compare output for output)
 
 A step = ray fetch (device-resident pool) -> sampler -> render_core forward -> loss -> backward -> [all-reduce]
 -> Adam.  Rank 0 prints ONE JSON line.  Extra objects:
@@ -127,6 +129,53 @@ def spawn_ranks_or_die(args):
     raise SystemExit(subprocess.call(cmd))
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20      # --dump-outputs: the array data of all files together (the .npy headers stay well inside 64 MB)
+
+
+def step_outputs(total, log, out, net):
+    """What a caller of the timed train step holds after its last step: the total loss, the loss log, the renderer's outputs, and the
+    module's parameters after the optimizer step together with the gradients that step applied."""
+    arrays = {'loss_total': total}
+    for prefix, d in (('log', log), ('out', out)):
+        for k, v in d.items():
+            if torch.is_tensor(v) and v.is_floating_point() and not k.startswith('_'):
+                arrays[f'{prefix}.{k}'] = v
+    for k, p in net.named_parameters():
+        arrays['param.' + k] = p
+        if p.grad is not None:
+            arrays['grad.' + k] = p.grad
+    return arrays
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES, seed=6033):
+    """Write every tensor of `arrays` as <path>/<name>.npy, float64 as float64 and every other float type as float32.  When they
+    exceed `budget` bytes together, each array larger than an equal share of what the smaller ones leave is replaced by a sample of
+    its flattened elements at sorted indices drawn from a generator seeded by `seed` and the name: the same arguments give the same
+    files on every run.  Returns a record for the result line."""
+    import zlib
+    host = {k: v.detach().to('cpu', torch.float64 if v.dtype == torch.float64 else torch.float32).contiguous().numpy()
+            for k, v in arrays.items()}
+    sizes = sorted((a.nbytes, k) for k, a in host.items())
+    cap, left = None, budget
+    for i, (nb, _) in enumerate(sizes):
+        share = left // (len(sizes) - i)
+        if nb > share:            # this one and every larger one are sampled down to `share` bytes
+            cap = share
+            break
+        left -= nb
+    os.makedirs(path, exist_ok=True)
+    sampled, written = {}, 0
+    for k, a in host.items():
+        if cap is not None and a.nbytes > cap:
+            n = cap // a.itemsize
+            idx = np.sort(np.random.default_rng([seed, zlib.crc32(k.encode())]).choice(a.size, n, replace=False))
+            sampled[k] = {"shape": list(a.shape), "elements": int(n)}
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + '.npy'), a)
+        written += a.nbytes
+    return {"dir": path, "arrays": len(host), "bytes": written, "sampled": sampled}
+
+
 class SumRuleError(RuntimeError):
     """The per-launch GEMM times of a bracketed step add up to more than that step's wall time: the launches overlapped
     (two streams) or the event pairing broke -- the roofline of such a step is not evidence."""
@@ -188,15 +237,18 @@ def stage2_leg(args):
     pool = (make_object_rays if args.object_rays else make_rays)(R * n, seed=6033)
     pool = {k: torch.from_numpy(v).to(dev) for k, v in pool.items() if k in ('rays_o', 'rays_d', 'rgbs')}
     entered = []
+    kept = {}
 
     def step(i):
         b = {k: v[i * R:(i + 1) * R] for k, v in pool.items()}
         opt.zero_grad(set_to_none=True)
         out = net.train_step_rays(b, 6000 + i)
-        total, _ = total_loss(out, losses, 6000 + i)
+        total, log = total_loss(out, losses, 6000 + i)
         total.backward()
         opt.step()
         entered.append(float(len(out['_paths']) > 1 and out['_paths'][1].shape[0]) / R)
+        if args.dump_outputs and i == n - 1:
+            kept.update(total=total, log=log, out=out)
         return total
     for i in range(args.warmup):
         step(i)
@@ -235,6 +287,7 @@ def stage2_leg(args):
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
     gc.enable()
+    dumped = dump_outputs(args.dump_outputs, step_outputs(kept['total'], kept['log'], kept['out'], net)) if args.dump_outputs else None
     if not args.no_kernel_timing:
         kts = [e.end_kernel_timing() for e in engines]
     step_ms = np.array([step_ev[i].elapsed_time(step_ev[i + 1]) for i in range(args.steps)])
@@ -252,6 +305,8 @@ def stage2_leg(args):
                                    "weights for the whole run -- a fixed-path measurement, not a training trajectory",
                    "frac_rays_entering_object": float(np.mean(entered)), "final_loss": float(last.detach()),
                    "max_mem_GB": torch.cuda.max_memory_allocated() / 2 ** 30}}
+    if dumped is not None:
+        res["dump_outputs"] = dumped
     if not args.no_kernel_timing and args.mlp_dtype == 'fp32':
         fl = sum(k['flops'] for k in kts); sec = sum(k['seconds'] for k in kts); ln = sum(k['launches'] for k in kts)
         tf = fl / max(sec, 1e-12) / 1e12
@@ -368,6 +423,7 @@ def stage1_leg(args, dist_ctx):
 
     eng = net.engine()
     stats = {'P_in': 0, 'P_out': 0}
+    kept = {}
 
     def one_step(it):
         step = args.start_step + it
@@ -378,19 +434,21 @@ def stage1_leg(args, dist_ctx):
         if not args.unfused_loss:
             # loss assembly on the HIP loss kernels; with a reducer the subset means take this rank's count ratios (n_local * world /
             # sum n, device scalars; the eikonal one INSIDE those kernels): the N > 1 step is the N = 1 step + two all-reduces
-            total, _, _ = fused_stage1_loss(net, batch_for(it), step, losses, reducer=reducer)
+            total, log, out = fused_stage1_loss(net, batch_for(it), step, losses, reducer=reducer)
         else:
             out = net.train_step_rays(batch_for(it), step)
             if reducer is not None:     # subset means over the union of all ranks' subsets (parallel.dp_weight_outputs)
                 from nu_nerf_amd.parallel import dp_weight_outputs
                 dp_weight_outputs(out, reducer, net)
-            total, _ = total_loss(out, losses, step)
+            total, log = total_loss(out, losses, step)
         total.backward()
         if reducer is not None:
             reducer.all_reduce()
         opt.step()
         stats['P_in'] += eng.last_ctx['P_in']
         stats['P_out'] += eng.last_ctx['P_out']
+        if args.dump_outputs and it == args.warmup + args.steps - 1:
+            kept.update(total=total, log=log, out=out)
         return total
 
     for it in range(args.warmup):
@@ -436,6 +494,7 @@ def stage1_leg(args, dist_ctx):
     ktime = eng.end_kernel_timing() if not args.no_kernel_timing else None
     if rank != 0:
         return None
+    dumped = dump_outputs(args.dump_outputs, step_outputs(kept['total'], kept['log'], kept['out'], net)) if args.dump_outputs else None
 
     ms = 1e3 * elapsed / args.steps
     value = R * world * args.steps / elapsed
@@ -471,6 +530,8 @@ def stage1_leg(args, dist_ctx):
                    "step_ms": [round(float(v), 2) for v in step_ms],
                    "new_device_segments_per_step": [seg_count[i + 1] - seg_count[i] for i in range(args.steps)]},
     }
+    if dumped is not None:
+        res["dump_outputs"] = dumped
     if ktime is not None:
         tf = ktime['flops'] / max(ktime['seconds'], 1e-12) / 1e12
         traffic, traffic_tn, traffic_src = find_traffic_profile(R, world, args.real_capture, args.mlp_dtype, args.object_rays,
@@ -541,6 +602,7 @@ def run_extra_legs(args, dist_ctx):
         a = argparse.Namespace(**vars(args))
         a.object_rays, a.real_capture, a.mlp_dtype, a.thick, a.unfused_loss, a.time_every, a.no_kernel_timing = False, False, 'fp32', False, False, 0, False
         a.start_step = 20000
+        a.dump_outputs = None           # the dump is the headline's
         for k, v in over.items():
             setattr(a, k, v)
         t0 = time.perf_counter()
@@ -590,7 +652,13 @@ def main():
     ap.add_argument('--time-every', type=int, default=0,
                     help='bracket the GEMM launches with HIP events on every Nth step of the timed region; 0 (default): on ONE '
                          'step in the middle of it (the ~330 event pairs cost that step 2-4 ms)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last one computed (loss, loss log, renderer outputs, parameters after '
+                         'the optimizer step, their gradients) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (arrays '
+                         'sampled at fixed seeded indices beyond that); rank 0 only')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     if args.workload == 'stage2':
         if int(os.environ.get('WORLD_SIZE', 1)) != 1 or args.gpus != 1:
             raise SystemExit("--workload stage2 runs on one GPU")

@@ -72,3 +72,41 @@ def test_traffic_of_a_pass_with_batched_launches_is_rescaled_to_the_runs_launch_
     assert abs(tn - d['gemm_tn_kernel']['hbm_bytes_per_launch']) < 1.0                      # 34 kernels = 34 event launches
     assert bench.find_traffic_profile(w['rays'], 1, True, 'bf16', False, True, w['mean_inner_points'], w['mean_outer_points'],
                                       nt_launches=80) == (None, None, None)
+
+
+def test_steps_below_one_is_refused():
+    r = _run(['--steps', '0', '--warmup', '0'], {})
+    assert r.returncode == 2 and '--steps must be at least 1' in r.stderr and '"metric"' not in r.stdout
+
+
+def test_dump_outputs_writes_the_step_results_within_the_budget(tmp_path):
+    """--dump-outputs: one float32 / float64 .npy per array a caller of the step holds; past the byte budget the large arrays are
+    sampled at seeded indices, identically on every run."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    net = torch.nn.Linear(300, 200)
+    net(torch.randn(5, 300)).sum().backward()
+    out = {'ray_rgb': torch.rand(64, 3), 'acc': torch.rand(64, dtype=torch.float64), 'half': torch.rand(10, dtype=torch.bfloat16),
+           'cand': torch.ones(64, dtype=torch.bool), '_paths': [torch.rand(3)], 'n': 3}
+    arrays = bench.step_outputs(torch.tensor(0.5), {'loss_rgb': torch.rand(64)}, out, net)
+    assert sorted(arrays) == ['grad.bias', 'grad.weight', 'log.loss_rgb', 'loss_total', 'out.acc', 'out.half', 'out.ray_rgb',
+                              'param.bias', 'param.weight']
+
+    rec = bench.dump_outputs(str(tmp_path / 'all'), arrays)
+    assert rec['arrays'] == 9 and not rec['sampled']
+    for k, v in arrays.items():
+        a = np.load(tmp_path / 'all' / (k + '.npy'))
+        assert a.dtype == (np.float64 if v.dtype == torch.float64 else np.float32) and a.shape == tuple(v.shape), k
+        np.testing.assert_array_equal(a, v.detach().double().numpy())
+
+    budget = 100_000                        # the 240 kB weight and its gradient must be cut to what the small arrays leave
+    recs = [bench.dump_outputs(str(tmp_path / d), arrays, budget=budget) for d in ('a', 'b')]
+    assert recs[0]['sampled'].keys() == {'param.weight', 'grad.weight'} and recs[0]['bytes'] <= budget
+    assert recs[0]['sampled']['param.weight']['shape'] == [200, 300]
+    for k in arrays:
+        a, b = np.load(tmp_path / 'a' / (k + '.npy')), np.load(tmp_path / 'b' / (k + '.npy'))
+        np.testing.assert_array_equal(a, b)
+    w = np.load(tmp_path / 'a' / 'param.weight.npy')
+    assert w.size == recs[0]['sampled']['param.weight']['elements'] and np.isin(w, net.weight.detach().numpy()).all()
