@@ -566,6 +566,37 @@ int nu_adam_desc_size(void);
 int nu_adam_step(const NuAdamDesc* descs_host, int n, double lr, double beta1, double beta2, double eps, int step,
                  hipStream_t stream);   /* hyper-parameters in double: 1 - beta and the bias corrections are formed as torch forms them */
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Mesh extraction (extract_mesh_stage1.py / _stage2.py: extract_geometry, network/field.py:1286-1317 -- PyMCubes on a host grid).
+ * Grid u[nx][ny][nz] fp32, C order (point p = (i ny + j) nz + k), nx, ny, nz >= 2; the workspace (nu_mc_workspace_bytes, 8-byte
+ * aligned) carries per-brick counts and offsets from one call to the next and must stay untouched in between.
+ *   nu_mc_count             per-brick vertex / triangle counts (a corner is inside when u < iso; tables: csrc/mc_tables.h)
+ *   nu_mc_scan              exclusive offsets of those counts; totals[2] (device, int64) = (Nv, Nf) -- the caller's one host read
+ *   nu_mc_write_vertices    V [Nv,3] in index space, ordered by (owner point, axis): point p owns its +x, +y, +z edges, a straddling
+ *                           edge gives one vertex at p + t e_axis, t = (iso - u_p) / (u_{p+e} - u_p); first_vid [nx ny nz] int32 gets
+ *                           the first vertex id of every owner (other entries are not written)
+ *   nu_mc_write_triangles   F [Nf,3] int32 ordered by (cell, table slot), normals (right-handed) towards u < iso
+ * Grid compaction for the SDF evaluation of a dense grid at points (X[i], Y[j], Z[k]) (extract_fields, field.py:1286-1307): a point is
+ * evaluated iff NOT torch.norm(x) >= 1, with torch's arithmetic ((x^2 + z^2) + y^2, correctly rounded sqrt).  Same workspace layout.
+ *   nu_grid_inside_count    counts + scan; chunk_rows[c] (device, int64, c = 0 .. ceil(npts / chunk_points)) = first compact row of the
+ *                           chunk of points [c chunk_points, (c+1) chunk_points); the last entry is the inside total.  chunk_points % 256 == 0
+ *   nu_grid_compact         the inside points of [p0, p0 + n) (p0 % 256 == 0) as x rows [P,3] in point order, row 0 = first inside point
+ *   nu_grid_scatter         u[p] = val[row of p] for the inside points of [p0, p0 + n), outside_val for the others
+ * --------------------------------------------------------------------------------------------------------- */
+long long nu_mc_workspace_bytes(int nx, int ny, int nz);
+int nu_mc_count(const float* u, int nx, int ny, int nz, float iso, void* workspace, long long workspace_bytes, hipStream_t stream);
+int nu_mc_scan(int nx, int ny, int nz, void* workspace, long long workspace_bytes, long long* totals, hipStream_t stream);
+int nu_mc_write_vertices(const float* u, int nx, int ny, int nz, float iso, const void* workspace, long long workspace_bytes, float* V,
+                         int* first_vid, hipStream_t stream);
+int nu_mc_write_triangles(const float* u, int nx, int ny, int nz, float iso, const void* workspace, long long workspace_bytes,
+                          const int* first_vid, int* F, hipStream_t stream);
+int nu_grid_inside_count(const float* X, const float* Y, const float* Z, int nx, int ny, int nz, long long chunk_points, void* workspace,
+                         long long workspace_bytes, long long* chunk_rows, hipStream_t stream);
+int nu_grid_compact(const float* X, const float* Y, const float* Z, int nx, int ny, int nz, long long p0, long long n,
+                    const void* workspace, long long workspace_bytes, float* rows, hipStream_t stream);
+int nu_grid_scatter(const float* X, const float* Y, const float* Z, int nx, int ny, int nz, long long p0, long long n,
+                    const void* workspace, long long workspace_bytes, const float* val, float outside_val, float* u, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,69 @@
+"""python -m nu_nerf_amd.extract_mesh --cfg CFG [--resolution 1024] [--ckpt PATH] [--out PATH] [--stage2]
+
+extract_mesh_stage1.py on the GPU: the renderer named by the config (`zero_thickness` picks the module set) loads
+data/model/{name}/model.pth (train_glue.save_checkpoint format), its SDF is sampled on the [-1,1]^3 grid (mesh.sdf_grid), marching
+cubes runs at threshold 0, the faces are flipped (np.fliplr: outward normals) and data/meshes/{name}-{step}.ply is written -- the
+file a stage-2 config's `stage1_mesh_dir` names.  The pymeshlab remeshing of the reference (`_simplified.ply`) is not done.
+
+--stage2: extract_mesh_stage2.py -- a stage-2 checkpoint; the field is the inner sdf where the stage-1 sdf is < 0 and 1 elsewhere
+(mesh.stage2_inner_grid), no face flip.
+"""
+import argparse
+import os
+import sys
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m nu_nerf_amd.extract_mesh", description=__doc__.split("\n\n")[1])
+    ap.add_argument('--cfg', type=str, required=True, help="training config (YAML)")
+    ap.add_argument('--resolution', type=int, default=1024, help="grid points per axis (default 1024)")
+    ap.add_argument('--ckpt', type=str, default=None, help="checkpoint (default data/model/{name}/model.pth)")
+    ap.add_argument('--out', type=str, default=None, help="output PLY (default data/meshes/{name}-{step}.ply)")
+    ap.add_argument('--stage2', action='store_true', help="inner surface of a stage-2 model (extract_mesh_stage2.py)")
+    ap.add_argument('--slab-points', type=int, default=None, help="grid points per SDF evaluation slab (default mesh.SLAB_POINTS)")
+    return ap.parse_args(argv)
+
+
+def _renderer(cfg):
+    if cfg.get('zero_thickness', True):
+        from .stage2 import name2renderer          # registers 'stage2' next to the stage-1 'shape'
+    else:
+        from .stage2_thick import name2renderer
+    return name2renderer[cfg['network']](cfg, training=False)
+
+
+def main(argv=None):
+    flags = parse_args(argv)
+    import numpy as np
+    import torch
+    import yaml
+    from . import mesh
+    from .train_glue import load_checkpoint
+
+    with open(flags.cfg) as fh:
+        cfg = yaml.safe_load(fh)
+    network = _renderer(cfg)
+    ckpt = flags.ckpt or f'data/model/{cfg["name"]}/model.pth'
+    _, step = load_checkpoint(ckpt, network, map_location='cpu')
+    network = network.eval().to(torch.device('cuda', torch.cuda.current_device()))
+    print(f'successfully load {cfg["name"]} step {step}!')
+    res = flags.resolution
+    if flags.stage2:
+        s1_ckpt = network.cfg.get('stage1_ckpt_dir')
+        if s1_ckpt and os.path.exists(s1_ckpt):                # extract_mesh_stage2.py:27-34: stage 1 from its own checkpoint
+            load_checkpoint(s1_ckpt, network.stage1_network, map_location='cpu')
+        u = mesh.stage2_inner_grid(network, res, slab_points=flags.slab_points)
+        V, F = mesh.marching_cubes(u, 0.0)
+        V, F = mesh._to_world(V, res, mesh.BOX_MIN, mesh.BOX_MAX), F.cpu().numpy()
+    else:
+        V, F = mesh.extract_mesh(network, res, 0.0, slab_points=flags.slab_points)
+        F = np.ascontiguousarray(np.fliplr(F))
+    out = flags.out or os.path.join('data', 'meshes', f'{cfg["name"]}-{step}.ply')
+    os.makedirs(os.path.dirname(out) or '.', exist_ok=True)
+    mesh.write_ply(out, V, F)
+    print(f'wrote {out}: {len(V)} vertices, {len(F)} triangles')
+    return out
+
+
+if __name__ == "__main__":
+    sys.exit(0 if main() else 1)
