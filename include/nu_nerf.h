@@ -308,6 +308,20 @@ int nu_lbvh_trace(const void* bvh, int n_faces, const float* rays, int N, float 
 /* O(N*F) sweep with the same ray/triangle test (cross-check, tiny meshes) */
 int nu_brute_trace(const float* V, const int* F, int n_faces, const float* rays, int N, float tmin, float tmax,
                    float* hit, int* idx, float* t_out, hipStream_t stream);
+/* closest point on the mesh to each query point (postprocess_stage2_mesh.py's Open3D compute_closest_points; mesh distances):
+ * pts [N,3];
+ *   d2[N]        squared distance |p - q|^2 in fp32 (no sqrt on the path),
+ *   idx[N]       face id of the closest triangle (ties in d2 -> lowest face id),
+ *   closest[N,3] q (may be NULL).
+ * Only triangles with d2 <= max_d2 count (pass +inf for no bound).  When none qualifies: idx = 10000000, d2 = +inf,
+ * closest = (0, 0, 0).  Point/triangle = the regions of Ericson, Real-Time Collision Detection 5.1.5, one rounding per operation in
+ * a fixed order; a zero-area triangle is the minimum over its three edges as segments.  Traverses the tree of nu_lbvh_build; two
+ * kernels on `stream`, no other stream. */
+int nu_lbvh_closest(const void* bvh, int n_faces, const float* pts, int N, float max_d2, float* d2, int* idx, float* closest,
+                    hipStream_t stream);
+/* O(N*F) sweep with the same point/triangle routine (cross-check; small meshes) */
+int nu_brute_closest(const float* V, const int* F, int n_faces, const float* pts, int N, float max_d2, float* d2, int* idx,
+                     float* closest, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Network-level entry points: one call sequences every kernel launch of a network pass from C++.

@@ -654,3 +654,244 @@ extern "C" int nu_brute_trace(const float* V, const int* F, int n_faces, const f
                        idx, t_out);
     return nu_launch_status();
 }
+
+// ------------------------------------------------------------------------------------------------
+// closest point on the mesh (postprocess of the stage-2 mesh, mesh distances).  Same tree, same file-wide single-rounding rule:
+// the LBVH result is defined bit-exactly against the O(N*F) sweep below and tests/closest_point_oracle.py.
+// ------------------------------------------------------------------------------------------------
+// closest point on the segment [a, b] (Ericson, Real-Time Collision Detection 5.1.2); a zero-length segment gives a
+static __device__ inline void nu_closest_seg(const float* p, const float* a, const float* b, float* q) {
+    float ab[3], ap[3];
+    for (int k = 0; k < 3; ++k) { ab[k] = b[k] - a[k]; ap[k] = p[k] - a[k]; }
+    const float t = nu_dot3_rn(ap, ab);
+    if (t <= 0.0f) { for (int k = 0; k < 3; ++k) q[k] = a[k]; return; }
+    const float den = nu_dot3_rn(ab, ab);
+    if (t >= den) { for (int k = 0; k < 3; ++k) q[k] = b[k]; return; }
+    const float s = t / den;
+    for (int k = 0; k < 3; ++k) q[k] = a[k] + ab[k] * s;
+}
+static __device__ inline float nu_dist2(const float* p, const float* q) {
+    float e[3];
+    for (int k = 0; k < 3; ++k) e[k] = p[k] - q[k];
+    return nu_dot3_rn(e, e);
+}
+// minimum over the three edges as segments, in the order ab, bc, ca (a later edge wins only when strictly nearer)
+static __device__ inline float nu_closest_edges(const float* p, const float* a, const float* b, const float* c, float* q) {
+    float q1[3];
+    nu_closest_seg(p, a, b, q);
+    float best = nu_dist2(p, q);
+    nu_closest_seg(p, b, c, q1);
+    float d = nu_dist2(p, q1);
+    if (d < best) { best = d; for (int k = 0; k < 3; ++k) q[k] = q1[k]; }
+    nu_closest_seg(p, c, a, q1);
+    d = nu_dist2(p, q1);
+    if (d < best) { best = d; for (int k = 0; k < 3; ++k) q[k] = q1[k]; }
+    return best;
+}
+// closest point q on the triangle abc to p and d2 = |p - q|^2: the vertex / edge / face regions of Ericson 5.1.5.  A triangle
+// with dot(n, n) == 0 (n = ab x ac: a zero-area sliver, as marching cubes emits) takes the minimum over its edges; so does a sliver
+// whose rounded face-region weights va, vb, vc are not all >= 0 with a positive sum -- this keeps q on the triangle (inside its
+// padded box, see nu_box_dist2) and finite.  No sqrt anywhere (hipcc's v_sqrt_f32 is not correctly rounded).
+static __device__ inline float nu_closest_tri(const float* p, const float* a, const float* b, const float* c, float* q) {
+    float ab[3], ac[3], n[3], ap[3], bp[3], cp[3];
+    for (int k = 0; k < 3; ++k) { ab[k] = b[k] - a[k]; ac[k] = c[k] - a[k]; }
+    nu_cross_rn(ab, ac, n);
+    if (nu_dot3_rn(n, n) == 0.0f) return nu_closest_edges(p, a, b, c, q);
+    for (int k = 0; k < 3; ++k) ap[k] = p[k] - a[k];
+    const float d1 = nu_dot3_rn(ab, ap), d2 = nu_dot3_rn(ac, ap);
+    if (d1 <= 0.0f && d2 <= 0.0f) { for (int k = 0; k < 3; ++k) q[k] = a[k]; return nu_dist2(p, q); }
+    for (int k = 0; k < 3; ++k) bp[k] = p[k] - b[k];
+    const float d3 = nu_dot3_rn(ab, bp), d4 = nu_dot3_rn(ac, bp);
+    if (d3 >= 0.0f && d4 <= d3) { for (int k = 0; k < 3; ++k) q[k] = b[k]; return nu_dist2(p, q); }
+    const float vc = d1 * d4 - d3 * d2;
+    if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) {
+        const float den = d1 - d3;                // >= 0; exactly 0 only where both dots round to 0 (a vanishing edge): take a
+        const float v = den > 0.0f ? d1 / den : 0.0f;
+        for (int k = 0; k < 3; ++k) q[k] = a[k] + ab[k] * v;
+        return nu_dist2(p, q);
+    }
+    for (int k = 0; k < 3; ++k) cp[k] = p[k] - c[k];
+    const float d5 = nu_dot3_rn(ab, cp), d6 = nu_dot3_rn(ac, cp);
+    if (d6 >= 0.0f && d5 <= d6) { for (int k = 0; k < 3; ++k) q[k] = c[k]; return nu_dist2(p, q); }
+    const float vb = d5 * d2 - d1 * d6;
+    if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) {
+        const float den = d2 - d6;
+        const float w = den > 0.0f ? d2 / den : 0.0f;
+        for (int k = 0; k < 3; ++k) q[k] = a[k] + ac[k] * w;
+        return nu_dist2(p, q);
+    }
+    const float va = d3 * d6 - d5 * d4;
+    const float e43 = d4 - d3, e56 = d5 - d6;
+    if (va <= 0.0f && e43 >= 0.0f && e56 >= 0.0f) {
+        const float den = e43 + e56;
+        const float w = den > 0.0f ? e43 / den : 0.0f;
+        for (int k = 0; k < 3; ++k) q[k] = b[k] + (c[k] - b[k]) * w;
+        return nu_dist2(p, q);
+    }
+    const float sum = (va + vb) + vc;
+    if (!(va >= 0.0f && vb >= 0.0f && vc >= 0.0f && sum > 0.0f)) return nu_closest_edges(p, a, b, c, q);
+    const float denom = 1.0f / sum;
+    const float v = vb * denom, w = vc * denom;
+    for (int k = 0; k < 3; ++k) q[k] = (a[k] + ab[k] * v) + ac[k] * w;
+    return nu_dist2(p, q);
+}
+
+// squared distance from p to the box (0 inside).  Conservative against nu_closest_tri: every q it returns lies on its triangle up to
+// the rounding of one convex combination, far below the eps the refit pads each leaf box with (lbvh_refit_kernel), so q is inside
+// every box that holds the triangle; per axis rn(p - q) is then at least rn(p - bmax) (or rn(bmin - p)) in magnitude, and
+// round-to-nearest squares and sums are monotone, so the computed box distance never exceeds the triangle's computed d2.
+static __device__ inline float nu_box_dist2(const float* p, const float* bmin, const float* bmax) {
+    float e[3];
+    for (int k = 0; k < 3; ++k) e[k] = fmaxf(fmaxf(bmin[k] - p[k], p[k] - bmax[k]), 0.0f);
+    return nu_dot3_rn(e, e);
+}
+
+// One query per lane over the binary nodes: depth first, the nearer child (box distance) first, a box culled only when its
+// distance is STRICTLY greater than the running best (an equal distance can still hold a lower face id), the best kept in
+// lexicographic (d2, face id) order and started at max_d2.  The stack holds (node, box distance) per lane in LDS,
+// wavefront-interleaved; a popped entry the running best has overtaken is skipped without its node being fetched.
+// First pass (RETRACE = false): a SHORT ring of STACK entries.  While the walk starts unbounded (max_d2 = inf) every level pushes,
+// so the ring drops its oldest entry instead of failing; a query that dropped one writes its best so far, marked
+// (idx = -1 - face id).  The second pass re-walks exactly the marked queries with the full NU_STACK (a Morton tree over 62-bit keys
+// is at most 62 deep) and starts from that best, which is a real candidate, so its bound is tight from the root on.
+template <int STACK, bool RETRACE, int WPB>
+__global__ __launch_bounds__(64 * WPB) void lbvh_closest_kernel(const char* __restrict__ buf, NuBvhLayout L, const float* __restrict__ pts,
+                                                                int N, float max_d2, float* __restrict__ d2out, int* __restrict__ idx,
+                                                                float* __restrict__ qout) {
+    static_assert((STACK & (STACK - 1)) == 0, "ring indexing needs a power of two");
+    __shared__ int snode[WPB][STACK][64];
+    __shared__ float sdist[WPB][STACK][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= N) return;
+    float best = max_d2;
+    int best_id = NU_MISS_INDEX;
+    if (RETRACE) {
+        const int m = idx[r];
+        if (m >= 0) return;
+        best_id = -1 - m;
+        if (best_id != NU_MISS_INDEX) best = d2out[r];
+    }
+    const NuBvhHeader* h = (const NuBvhHeader*)(buf + L.header);
+    const NuBvhNode* nodes = (const NuBvhNode*)(buf + L.nodes);
+    const float* tris = (const float*)(buf + L.tris);
+    const int* ids = (const int*)(buf + L.ids);
+    const int n = h->n_faces;
+    float p[3];
+    for (int k = 0; k < 3; ++k) p[k] = pts[r * 3LL + k];
+    float bq[3] = {0.f, 0.f, 0.f};
+    bool improved = false;
+
+    auto test_leaf = [&](int pos) {
+        const float4* tp = (const float4*)(tris + pos * 12LL);
+        const float4 A = tp[0], B = tp[1], C = tp[2];
+        const float a[3] = {A.x, A.y, A.z}, b[3] = {B.x, B.y, B.z}, c[3] = {C.x, C.y, C.z};
+        float q[3];
+        const float d = nu_closest_tri(p, a, b, c, q);
+        const int id = ids[pos];
+        if (d < best || (d == best && id < best_id)) {
+            best = d; best_id = id; improved = true;
+            for (int k = 0; k < 3; ++k) bq[k] = q[k];
+        }
+    };
+
+    bool dropped = false;
+    if (n == 1) {
+        test_leaf(0);
+    } else {
+        int top = 0, cnt = 0;            // ring: entries top - cnt .. top - 1 (mod STACK), the newest at top - 1
+        int node = 0;
+        while (true) {
+            const NuBvhNode nd = nodes[node];
+            const float dl = nu_box_dist2(p, nd.lmin, nd.lmax), dr = nu_box_dist2(p, nd.rmin, nd.rmax);
+            if (nd.left < 0 && dl <= best) test_leaf(-1 - nd.left);
+            if (nd.right < 0 && dr <= best) test_leaf(-1 - nd.right);
+            const bool il = nd.left >= 0 && dl <= best, ir = nd.right >= 0 && dr <= best;
+            int next = -1;
+            if (il && ir) {
+                const bool left_first = dl <= dr;
+                next = left_first ? nd.left : nd.right;
+                snode[w][top][lane] = left_first ? nd.right : nd.left;
+                sdist[w][top][lane] = left_first ? dr : dl;
+                top = (top + 1) & (STACK - 1);
+                if (cnt < STACK) ++cnt;
+                else dropped = true;     // the oldest entry was overwritten (never in the full-stack pass: depth <= 62)
+            } else if (il) {
+                next = nd.left;
+            } else if (ir) {
+                next = nd.right;
+            }
+            while (next < 0 && cnt > 0) {
+                top = (top - 1) & (STACK - 1);
+                --cnt;
+                if (sdist[w][top][lane] <= best) next = snode[w][top][lane];
+            }
+            if (next < 0) break;
+            node = next;
+        }
+    }
+    if (!RETRACE && dropped) {           // incomplete: the second pass finishes this query from its best so far
+        idx[r] = -1 - best_id;
+        if (best_id != NU_MISS_INDEX) {
+            d2out[r] = best;
+            if (qout) for (int k = 0; k < 3; ++k) qout[r * 3LL + k] = bq[k];
+        }
+        return;
+    }
+    if (RETRACE && !improved) {          // the first pass's candidate stands (its d2 and point are already written)
+        idx[r] = best_id;
+        if (best_id != NU_MISS_INDEX) return;
+    }
+    const bool hit = best_id != NU_MISS_INDEX;
+    d2out[r] = hit ? best : __int_as_float(0x7f800000);
+    idx[r] = best_id;
+    if (qout) for (int k = 0; k < 3; ++k) qout[r * 3LL + k] = hit ? bq[k] : 0.0f;
+}
+
+#define NU_CLOSEST_SHORT 16
+extern "C" int nu_lbvh_closest(const void* bvh, int n_faces, const float* pts, int N, float max_d2, float* d2, int* idx, float* closest,
+                               hipStream_t stream) {
+    if (N <= 0) return NU_OK;
+    if (n_faces <= 0 || !bvh || !pts || !d2 || !idx) return NU_ERR_ARG;
+    const NuBvhLayout L = nu_bvh_layout(n_faces);
+    // both passes on the caller's stream, in order: the second reads the marks the first wrote
+    hipLaunchKernelGGL((lbvh_closest_kernel<NU_CLOSEST_SHORT, false, 4>), dim3(nu_cdiv(N, 256)), dim3(256), 0, stream, (const char*)bvh, L,
+                       pts, N, max_d2, d2, idx, closest);
+    hipLaunchKernelGGL((lbvh_closest_kernel<NU_STACK, true, 1>), dim3(nu_cdiv(N, 64)), dim3(64), 0, stream, (const char*)bvh, L, pts, N,
+                       max_d2, d2, idx, closest);
+    return nu_launch_status();
+}
+
+// brute-force closest point on the device (same point/triangle routine; O(N*F)): cross-check + small meshes
+__global__ __launch_bounds__(256) void brute_closest_kernel(const float* __restrict__ V, const int* __restrict__ F, int nf,
+                                                            const float* __restrict__ pts, int N, float max_d2, float* __restrict__ d2out,
+                                                            int* __restrict__ idx, float* __restrict__ qout) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= N) return;
+    float p[3];
+    for (int k = 0; k < 3; ++k) p[k] = pts[r * 3LL + k];
+    float best = max_d2, bq[3] = {0.f, 0.f, 0.f};
+    int best_id = NU_MISS_INDEX;
+    for (int f = 0; f < nf; ++f) {
+        float v[3][3], q[3];
+        for (int a = 0; a < 3; ++a)
+            for (int k = 0; k < 3; ++k) v[a][k] = V[F[f * 3 + a] * 3LL + k];
+        const float d = nu_closest_tri(p, v[0], v[1], v[2], q);
+        if (d < best || (d == best && best_id == NU_MISS_INDEX)) {      // ascending f: ties keep the lowest id
+            best = d; best_id = f;
+            for (int k = 0; k < 3; ++k) bq[k] = q[k];
+        }
+    }
+    const bool hit = best_id != NU_MISS_INDEX;
+    d2out[r] = hit ? best : __int_as_float(0x7f800000);
+    idx[r] = best_id;
+    if (qout) for (int k = 0; k < 3; ++k) qout[r * 3LL + k] = hit ? bq[k] : 0.0f;
+}
+extern "C" int nu_brute_closest(const float* V, const int* F, int n_faces, const float* pts, int N, float max_d2, float* d2, int* idx,
+                                float* closest, hipStream_t stream) {
+    if (N <= 0) return NU_OK;
+    if (n_faces <= 0 || !V || !F || !pts || !d2 || !idx) return NU_ERR_ARG;
+    hipLaunchKernelGGL(brute_closest_kernel, dim3(nu_cdiv(N, 256)), dim3(256), 0, stream, V, F, n_faces, pts, N, max_d2, d2, idx,
+                       closest);
+    return nu_launch_status();
+}

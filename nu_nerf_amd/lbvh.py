@@ -17,6 +17,10 @@ from . import _lib as L
 MISS_INDEX = 10000000
 
 
+class EmptyMeshError(ValueError, L.NuNerfLibraryError):
+    """An LBVH over no triangles.  A ValueError; also the library error an empty mesh raised before this class existed."""
+
+
 class LBVH:
     def __init__(self, vertices, faces):
         L.require_cuda(vertices, faces)
@@ -25,6 +29,8 @@ class LBVH:
         self.V = vertices.detach().to(torch.float32).contiguous()
         self.F = faces.detach().to(torch.int32).contiguous()
         self.n_faces = int(self.F.shape[0])
+        if self.n_faces == 0 or self.V.shape[0] == 0:
+            raise EmptyMeshError("LBVH: the mesh has no triangles")
         nbytes = self.lib.nu_lbvh_bytes(self.n_faces)
         self.buf = torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=self.V.device)
         L.check(self.lib.nu_lbvh_build(L.ptr(self.V), int(self.V.shape[0]), L.ptr(self.F), self.n_faces, L.ptr(self.buf),
@@ -49,6 +55,39 @@ class LBVH:
         L.check(self.lib.nu_brute_trace(L.ptr(self.V), L.ptr(self.F), self.n_faces, L.ptr(ray), N, ctypes.c_float(tmin),
                                         ctypes.c_float(tmax), L.ptr(hit), L.ptr(idx), L.ptr(None), L.stream()), "nu_brute_trace")
         return hit, idx
+
+    def _closest(self, fn, args, points, max_dist):
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError(f"closest_points: points must be [N,3], got {tuple(points.shape)}")
+        L.require_cuda(points)
+        pts = points.detach().to(device=self.V.device, dtype=torch.float32).contiguous()
+        N = int(pts.shape[0])
+        d2 = torch.empty(N, dtype=torch.float32, device=pts.device)
+        idx = torch.empty(N, dtype=torch.int32, device=pts.device)
+        closest = torch.empty(N, 3, dtype=torch.float32, device=pts.device)
+        if N == 0:
+            return d2, idx, closest
+        if not bool(torch.isfinite(pts).all()):
+            raise ValueError("closest_points: query points must be finite")
+        if max_dist is None:
+            max_d2 = math.inf
+        else:
+            if not max_dist >= 0:
+                raise ValueError(f"closest_points: max_dist must be >= 0, got {max_dist}")
+            max_d2 = float(max_dist) * float(max_dist)     # float64 square, rounded once to fp32 by the call
+        L.check(getattr(self.lib, fn)(*args, L.ptr(pts), N, ctypes.c_float(max_d2), L.ptr(d2), L.ptr(idx), L.ptr(closest),
+                                      L.stream()), fn)
+        return d2, idx, closest
+
+    def closest_points(self, points, max_dist=None):
+        """Closest point on the mesh to each of points [N,3] -> (d2 f32 [N] = |p - q|^2, idx i32 [N] face id, closest f32 [N,3] q).
+        Ties in d2 go to the lowest face id.  Only faces within max_dist count (None: no bound); where none does the triple is
+        (+inf, MISS_INDEX, 0).  Bit-identical to closest_points_brute.  One host read (the finiteness check of the points)."""
+        return self._closest("nu_lbvh_closest", (L.ptr(self.buf), self.n_faces), points, max_dist)
+
+    def closest_points_brute(self, points, max_dist=None):
+        """O(N*F) device sweep with the same point/triangle routine (cross-check; small meshes)."""
+        return self._closest("nu_brute_closest", (L.ptr(self.V), L.ptr(self.F), self.n_faces), points, max_dist)
 
 
 def corner_angles_and_face_normals(tri):

@@ -6,6 +6,10 @@ run PyMCubes on a host grid: network/field.py:1286-1317).
   extract_geometry  field.py:1310-1317 with any query_func, the grid kept on the device
   extract_mesh      the fast path: sdf_grid of a renderer's SDF + marching cubes, world coordinates
   write_ply         binary little-endian PLY that stage2.read_ply reads back unchanged
+  read_ply          its inverse for any triangle PLY (ascii / binary little-endian, float / double, extra properties)
+  remove_faces_near postprocess_stage2_mesh.py: drop the inner faces that lie on the outer shell (LBVH closest points)
+  sample_surface    area-weighted deterministic surface samples on the device
+  mesh_distance     Chamfer / Hausdorff distances of two meshes from surface samples and LBVH closest points
 
 Conventions (DESIGN.md "Mesh extraction"): a grid point is INSIDE when u < threshold; triangles wind so that their right-handed
 normal points inside, which is where the reference's raw PyMCubes output of an sdf (positive outside) points before the face flip of
@@ -210,3 +214,179 @@ def write_ply(path, V, F):
         fh.write(header.encode('ascii'))
         fh.write(V.tobytes())
         fh.write(faces.tobytes())
+
+
+_PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',
+              'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
+
+
+def _ply_type(name, path):
+    if name not in _PLY_TYPES:
+        raise ValueError(f"read_ply: {path}: unsupported property type {name!r}")
+    return np.dtype('<' + _PLY_TYPES[name])
+
+
+def _ply_header(data, path):
+    end = data.find(b'end_header')
+    if not data.startswith(b'ply') or end < 0:
+        raise ValueError(f"read_ply: {path} is not a PLY file")
+    body = data.index(b'\n', end) + 1
+    fmt, elements = None, []                    # elements: [name, count, [(prop, type) or (prop, (count type, index type))]]
+    for line in data[:end].decode('ascii', 'replace').splitlines()[1:]:
+        tok = line.split()
+        if not tok or tok[0] in ('comment', 'obj_info'):
+            continue
+        if tok[0] == 'format':
+            fmt = tok[1]
+        elif tok[0] == 'element':
+            elements.append((tok[1], int(tok[2]), []))
+        elif tok[0] == 'property' and elements:
+            if tok[1] == 'list':
+                elements[-1][2].append((tok[4], (_ply_type(tok[2], path), _ply_type(tok[3], path))))
+            else:
+                elements[-1][2].append((tok[2], _ply_type(tok[1], path)))
+    if fmt == 'binary_big_endian':
+        raise ValueError(f"read_ply: {path}: big-endian PLY is not supported")
+    if fmt not in ('ascii', 'binary_little_endian'):
+        raise ValueError(f"read_ply: {path}: unknown format {fmt!r}")
+    return fmt, elements, body
+
+
+def read_ply(path):
+    """Triangle mesh from a PLY file -> (V float32 [Nv,3], F int32 [Nf,3]); the inverse of write_ply.  Reads ascii and binary
+    little-endian files with float or double coordinates; other vertex properties (normals, colours) and other elements without
+    lists are skipped; the face list may count in uchar / int / uint and index in int / uint.  Refuses non-triangle faces,
+    big-endian files and face indices outside the vertices."""
+    path = str(path)
+    with open(path, 'rb') as fh:
+        data = fh.read()
+    fmt, elements, off = _ply_header(data, path)
+    V = F = None
+    tokens = data[off:].decode('ascii', 'replace').split() if fmt == 'ascii' else None
+    ti = 0
+    for name, count, props in elements:
+        lists = [p for p, t in props if isinstance(t, tuple)]
+        if name == 'vertex' and lists:
+            raise ValueError(f"read_ply: {path}: list properties on vertices are not supported")
+        if name == 'face' and len(lists) != 1:
+            raise ValueError(f"read_ply: {path}: a face element needs exactly one list property")
+        if name not in ('vertex', 'face') and lists:
+            raise ValueError(f"read_ply: {path}: element {name!r} with a list property is not supported")
+        if fmt == 'ascii':
+            if name == 'face':
+                F = np.empty((count, 3), np.int64)
+                for r in range(count):
+                    for p, t in props:
+                        if isinstance(t, tuple):
+                            n = int(tokens[ti])
+                            if n != 3:
+                                raise ValueError(f"read_ply: {path}: face {r} has {n} vertices; only triangles are supported")
+                            F[r] = [int(x) for x in tokens[ti + 1: ti + 4]]
+                            ti += 4
+                        else:
+                            ti += 1
+            else:
+                width = len(props)
+                vals = tokens[ti: ti + count * width]
+                if len(vals) < count * width:
+                    raise ValueError(f"read_ply: {path}: file is truncated")
+                ti += count * width
+                if name == 'vertex':
+                    rows = np.asarray(vals, np.float64).reshape(count, width)
+                    cols = [[p for p, _ in props].index(c) for c in 'xyz']
+                    V = rows[:, cols].astype(np.float32)
+            continue
+        fields = []
+        for p, t in props:
+            fields += [('n', t[0]), ('i', t[1], (3,))] if isinstance(t, tuple) else [(p, t)]
+        dt = np.dtype(fields)
+        fit = min(count, max(0, (len(data) - off) // dt.itemsize))
+        rec = np.frombuffer(data, dtype=dt, count=fit, offset=off)
+        if name == 'face':
+            bad = np.nonzero(rec['n'] != 3)[0]     # records up to the first non-triangle are laid out as assumed
+            if len(bad):
+                raise ValueError(f"read_ply: {path}: face {int(bad[0])} has {int(rec['n'][bad[0]])} vertices; only triangles are "
+                                 "supported")
+        if fit < count:
+            raise ValueError(f"read_ply: {path}: file is truncated")
+        off += count * dt.itemsize
+        if name == 'vertex':
+            V = np.stack([rec['x'], rec['y'], rec['z']], 1).astype(np.float32)
+        elif name == 'face':
+            F = rec['i'].astype(np.int64)
+    if V is None:
+        raise ValueError(f"read_ply: {path}: no vertex element")
+    if F is None:
+        F = np.zeros((0, 3), np.int64)
+    if F.size and (F.min() < 0 or F.max() >= len(V)):
+        raise ValueError(f"read_ply: {path}: face index out of range (vertices: {len(V)})")
+    return np.ascontiguousarray(V), np.ascontiguousarray(F, dtype=np.int32)
+
+
+def _device():
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+def _as_device_mesh(V, F, dev):
+    V = V if torch.is_tensor(V) else torch.from_numpy(np.ascontiguousarray(V, dtype=np.float32))
+    F = F if torch.is_tensor(F) else torch.from_numpy(np.ascontiguousarray(F, dtype=np.int32))
+    return V.to(device=dev, dtype=torch.float32).contiguous(), F.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def remove_faces_near(V_in, F_in, V_out, F_out, min_dist=0.055):
+    """postprocess_stage2_mesh.py: keep the faces of the inner mesh (V_in, F_in) whose three vertices all lie farther than min_dist
+    from the outer mesh (V_out, F_out) -- faces on the outer shell, where the stage-2 field's torch.where seam makes a surface, go.
+    Each inner vertex's distance is np.linalg.norm(v - closest) in float64 from the fp32 closest point on the outer mesh (the
+    reference's Open3D compute_closest_points, here LBVH.closest_points).  Returns numpy (V float32, F int32): faces in their
+    order, the vertices no kept face references dropped and the rest in their order, reindexed.  (The reference's trimesh
+    update_faces + PLY export keeps every vertex; the kept triangles are the same.)"""
+    from .lbvh import LBVH
+    Vi = np.ascontiguousarray(V_in.cpu().numpy() if torch.is_tensor(V_in) else V_in, dtype=np.float32).reshape(-1, 3)
+    Fi = np.asarray(F_in.cpu().numpy() if torch.is_tensor(F_in) else F_in, dtype=np.int64).reshape(-1, 3)
+    dev = _device()
+    bvh = LBVH(*_as_device_mesh(V_out, F_out, dev))
+    _, _, q = bvh.closest_points(torch.from_numpy(Vi).to(dev))
+    dist = np.linalg.norm(Vi.astype(np.float64) - q.cpu().numpy().astype(np.float64), axis=-1)
+    keep = (dist > min_dist)[Fi].all(axis=1)
+    F = Fi[keep]
+    used = np.zeros(len(Vi), bool)
+    used[F.reshape(-1)] = True
+    remap = np.cumsum(used) - 1
+    return Vi[used], remap[F].astype(np.int32).reshape(-1, 3)
+
+
+def sample_surface(V, F, n, seed=0):
+    """n points [n,3] float32 on the device, uniform over the mesh's area: a face by the inverse CDF of the cumulative face areas
+    (float64, torch.searchsorted), a point in it by the square-root barycentric map; the uniforms come from a CPU generator
+    seeded with `seed`, so a seed gives the same points on every run.  Zero-area faces are never drawn."""
+    V, F = _as_device_mesh(V, F, V.device if torch.is_tensor(V) and V.is_cuda else _device())
+    n = int(n)
+    if len(F) == 0:
+        raise ValueError("sample_surface: the mesh has no triangles")
+    tri = V.double()[F.long()]
+    a, b, c = tri[:, 0], tri[:, 1], tri[:, 2]
+    cdf = torch.cumsum(0.5 * torch.linalg.norm(torch.cross(b - a, c - a, dim=1), dim=1), 0)
+    total = cdf[-1]
+    if not float(total) > 0:
+        raise ValueError("sample_surface: the mesh has no area")
+    g = torch.Generator().manual_seed(int(seed))
+    u = torch.rand(n, 3, dtype=torch.float64, generator=g).to(V.device)
+    fi = torch.searchsorted(cdf, u[:, 0] * total, right=True).clamp_(max=len(F) - 1)
+    r1, r2 = torch.sqrt(u[:, 1:2]), u[:, 2:3]
+    p = a[fi] * (1.0 - r1) + b[fi] * (r1 * (1.0 - r2)) + c[fi] * (r1 * r2)
+    return p.to(torch.float32)
+
+
+def mesh_distance(A, B, n_samples=1_000_000, seed=0):
+    """Distances between the meshes A = (V, F) and B from n_samples surface samples of each (sample_surface, the same seed for
+    both, so swapping A and B swaps the directions exactly) and closest points on the other mesh (LBVH.closest_points):
+    a_to_b_mean, b_to_a_mean, chamfer (their mean), a_to_b_max, b_to_a_max, hausdorff (the larger maximum)."""
+    from .lbvh import LBVH
+    dev = _device()
+    (VA, FA), (VB, FB) = _as_device_mesh(*A, dev), _as_device_mesh(*B, dev)
+    bvh_a, bvh_b = LBVH(VA, FA), LBVH(VB, FB)
+    d_ab = bvh_b.closest_points(sample_surface(VA, FA, n_samples, seed))[0].double().sqrt()
+    d_ba = bvh_a.closest_points(sample_surface(VB, FB, n_samples, seed))[0].double().sqrt()
+    ab_mean, ba_mean, ab_max, ba_max = (float(x) for x in torch.stack([d_ab.mean(), d_ba.mean(), d_ab.max(), d_ba.max()]).cpu())
+    return dict(a_to_b_mean=ab_mean, b_to_a_mean=ba_mean, chamfer=(ab_mean + ba_mean) / 2, a_to_b_max=ab_max, b_to_a_max=ba_max,
+                hausdorff=max(ab_max, ba_max))
