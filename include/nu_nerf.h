@@ -611,6 +611,57 @@ int nu_grid_compact(const float* X, const float* Y, const float* Z, int nx, int 
 int nu_grid_scatter(const float* X, const float* Y, const float* Z, int nx, int ny, int nz, long long p0, long long n,
                     const void* workspace, long long workspace_bytes, const float* val, float outside_val, float* u, hipStream_t stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Isotropic remeshing (extract_mesh_stage1.py:44-50: pymeshlab meshing_isotropic_explicit_remeshing; Botsch & Kobbelt 2004), one
+ * pass per entry; the driver (nu_nerf_amd/remesh.py) sorts and scans between them.  V fp32 [nv,3], F int32 [nf,3] (a dead face is
+ * (-1,-1,-1)), half-edge h = 3 f + s from F[f][s] to F[f][(s+1)%3], nh = 3 nf.  Every buffer is the caller's and sized by these
+ * counts, so there is no opaque workspace (and no workspace-bytes query).
+ *   nu_rm_edge_keys        keys[nh] int64 = (min << 32 | max) of each half-edge's vertices, INT64_MAX for a dead face
+ *   nu_rm_edges            from the STABLY sorted keys and their permutation (int64): E[nh,4] int32 per sorted slot = (h0, h1,
+ *                          half-edge count, locked) at the first slot of each run (= the edge id; count 0 elsewhere), he_edge[nh]
+ *                          (edge id per half-edge, -1 dead), vlock / vbound[nv] u8 (zeroed here): locked = on an edge with a count
+ *                          other than 2 or two same-way half-edges; boundary = on a one-face edge
+ *   mesh tables (RM args)  V, nv, F, nf, E, he_edge, vc_off [nv+1], vc_corner [3 nf] (corners sorted by vertex, then corner id:
+ *                          the stable sort of F), vlock, vbound
+ *   nu_rm_split_count      eflag[nh] = unlocked edge with |ab|^2 > max_len2; fcnt[nf] = 1 + split edges of the face (0: dead)
+ *   nu_rm_split_write      voff / foff (int64, exclusive scans of eflag / fcnt) -> Vout [nv + splits, 3] (V, then (a + b) * 0.5
+ *                          in edge-id order), Fout (per face its template's faces in slot order)
+ *   nu_rm_collapse_count   npts[nh] = 4 x rewritten faces of each collapse candidate (|ab|^2 < min_len2, link condition, no new
+ *                          edge above max_len2, no zero-area or flipped face), 0 for the rest
+ *   nu_rm_collapse_points  their query points (centroid + 3 edge midpoints per rewritten face) at 3 poff[e] (int64 exclusive scan)
+ *   nu_rm_collapse_claim   pidx = nu_lbvh_closest face ids of the points under the surface-distance bound; ckey[nh] (u64), claim[nv]
+ *                          (u64, reset here) and win[nh] int32: the candidates holding the atomicMin of their key at every vertex
+ *                          of their endpoints' faces
+ *   nu_rm_collapse_apply   the winners merged (V_io, F_io may alias V, F)
+ *   nu_rm_flip_*           the same for valence-lowering flips (claim over the edge's four vertices); cos2_max = cos^2 of the
+ *                          largest normal turn allowed
+ *   nu_rm_relax            Vout = tangential relaxation of every unlocked vertex (area-weighted centroid of its faces, projected
+ *                          on the plane of the area-weighted normal); nu_rm_project: Vout = closest (unlocked) or V (locked)
+ * --------------------------------------------------------------------------------------------------------- */
+int nu_rm_edge_keys(const int* F, int nf, long long* keys, hipStream_t stream);
+int nu_rm_edges(const int* F, int nf, int nv, const long long* skeys, const long long* perm, int* E, int* he_edge, unsigned char* vlock,
+                unsigned char* vbound, hipStream_t stream);
+int nu_rm_split_count(const float* V, const int* F, int nf, const int* E, const int* he_edge, float max_len2, int* eflag, int* fcnt,
+                      hipStream_t stream);
+int nu_rm_split_write(const float* V, int nv, const int* F, int nf, const int* E, const int* he_edge, const int* eflag,
+                      const long long* voff, const long long* foff, float* Vout, int* Fout, hipStream_t stream);
+#define NU_RM_ARGS const float *V, int nv, const int *F, int nf, const int *E, const int *he_edge, const int *vc_off, \
+                   const int *vc_corner, const unsigned char *vlock, const unsigned char *vbound
+int nu_rm_collapse_count(NU_RM_ARGS, float min_len2, float max_len2, int* npts, hipStream_t stream);
+int nu_rm_collapse_points(NU_RM_ARGS, float min_len2, float max_len2, const int* npts, const long long* poff, float* pts,
+                          hipStream_t stream);
+int nu_rm_collapse_claim(NU_RM_ARGS, const int* npts, const long long* poff, const int* pidx, unsigned long long* ckey,
+                         unsigned long long* claim, int* win, hipStream_t stream);
+int nu_rm_collapse_apply(NU_RM_ARGS, const int* win, float* V_io, int* F_io, hipStream_t stream);
+int nu_rm_flip_count(NU_RM_ARGS, float cos2_max, int* npts, hipStream_t stream);
+int nu_rm_flip_points(NU_RM_ARGS, float cos2_max, const int* npts, const long long* poff, float* pts, hipStream_t stream);
+int nu_rm_flip_claim(NU_RM_ARGS, float cos2_max, const int* npts, const long long* poff, const int* pidx, unsigned long long* ckey,
+                     unsigned long long* claim, int* win, hipStream_t stream);
+int nu_rm_flip_apply(NU_RM_ARGS, const int* win, int* F_io, hipStream_t stream);
+int nu_rm_relax(NU_RM_ARGS, float* Vout, hipStream_t stream);
+int nu_rm_project(const float* V, int nv, const unsigned char* vlock, const float* closest, float* Vout, hipStream_t stream);
+#undef NU_RM_ARGS
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,9 +1,10 @@
-"""python -m nu_nerf_amd.extract_mesh --cfg CFG [--resolution 1024] [--ckpt PATH] [--out PATH] [--stage2]
+"""python -m nu_nerf_amd.extract_mesh --cfg CFG [--resolution 1024] [--ckpt PATH] [--out PATH] [--stage2] [--remesh]
 
 extract_mesh_stage1.py on the GPU: the renderer named by the config (`zero_thickness` picks the module set) loads
 data/model/{name}/model.pth (train_glue.save_checkpoint format), its SDF is sampled on the [-1,1]^3 grid (mesh.sdf_grid), marching
 cubes runs at threshold 0, the faces are flipped (np.fliplr: outward normals) and data/meshes/{name}-{step}.ply is written -- the
-file a stage-2 config's `stage1_mesh_dir` names.  The pymeshlab remeshing of the reference (`_simplified.ply`) is not done.
+raw mesh.  --remesh also writes data/meshes/{name}-{step}_simplified.ply (the file the stage-2 configs' `stage1_mesh_dir` names):
+the reference's pymeshlab isotropic remeshing at 0.5 % of the bounding-box diagonal, here remesh.remesh_isotropic on the GPU.
 
 --stage2: extract_mesh_stage2.py -- a stage-2 checkpoint; the field is the inner sdf where the stage-1 sdf is < 0 and 1 elsewhere
 (mesh.stage2_inner_grid), no face flip.
@@ -20,6 +21,7 @@ def parse_args(argv=None):
     ap.add_argument('--ckpt', type=str, default=None, help="checkpoint (default data/model/{name}/model.pth)")
     ap.add_argument('--out', type=str, default=None, help="output PLY (default data/meshes/{name}-{step}.ply)")
     ap.add_argument('--stage2', action='store_true', help="inner surface of a stage-2 model (extract_mesh_stage2.py)")
+    ap.add_argument('--remesh', action='store_true', help="also write the isotropically remeshed OUT_simplified.ply")
     ap.add_argument('--slab-points', type=int, default=None, help="grid points per SDF evaluation slab (default mesh.SLAB_POINTS)")
     return ap.parse_args(argv)
 
@@ -62,6 +64,12 @@ def main(argv=None):
     os.makedirs(os.path.dirname(out) or '.', exist_ok=True)
     mesh.write_ply(out, V, F)
     print(f'wrote {out}: {len(V)} vertices, {len(F)} triangles')
+    if flags.remesh:
+        from .remesh import remesh_isotropic, simplified_path
+        Vs, Fs = remesh_isotropic(V, F)
+        out_s = simplified_path(out)
+        mesh.write_ply(out_s, Vs, Fs)
+        print(f'wrote {out_s}: {len(Vs)} vertices, {len(Fs)} triangles')
     return out
 
 

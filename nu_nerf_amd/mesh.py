@@ -10,6 +10,7 @@ run PyMCubes on a host grid: network/field.py:1286-1317).
   remove_faces_near postprocess_stage2_mesh.py: drop the inner faces that lie on the outer shell (LBVH closest points)
   sample_surface    area-weighted deterministic surface samples on the device
   mesh_distance     Chamfer / Hausdorff distances of two meshes from surface samples and LBVH closest points
+  remesh_isotropic  isotropic explicit remeshing (split / collapse / flip / relax on the device: remesh.py, csrc/remesh.hip)
 
 Conventions (DESIGN.md "Mesh extraction"): a grid point is INSIDE when u < threshold; triangles wind so that their right-handed
 normal points inside, which is where the reference's raw PyMCubes output of an sdf (positive outside) points before the face flip of
@@ -390,3 +391,9 @@ def mesh_distance(A, B, n_samples=1_000_000, seed=0):
     ab_mean, ba_mean, ab_max, ba_max = (float(x) for x in torch.stack([d_ab.mean(), d_ba.mean(), d_ab.max(), d_ba.max()]).cpu())
     return dict(a_to_b_mean=ab_mean, b_to_a_mean=ba_mean, chamfer=(ab_mean + ba_mean) / 2, a_to_b_max=ab_max, b_to_a_max=ba_max,
                 hausdorff=max(ab_max, ba_max))
+
+
+def remesh_isotropic(V, F, target_len=None, max_surf_dist=None, iterations=3, stats=None):
+    """Isotropic explicit remeshing on the GPU (the reference's pymeshlab step before stage 2): see remesh.remesh_isotropic."""
+    from .remesh import remesh_isotropic as _remesh
+    return _remesh(V, F, target_len=target_len, max_surf_dist=max_surf_dist, iterations=iterations, stats=stats)
