@@ -228,13 +228,11 @@ struct FsNet16 {
     int Kp[8], N[8];
 };
 
-// WR = 2: 512 threads, two row groups of four waves share one weight stream (128 rows per workgroup: half the weight bytes per point
-// through L2 -> LDS, which is what bounds this kernel -- every tile re-streams the whole network, 0.95 MB); one workgroup per CU.
-template <int TMN, int WR>
-__global__ __launch_bounds__(256 * WR, WR == 1 ? 2 : 1) void sdf_fused16_fwd_kernel(FsNet16 net, const float* __restrict__ X, int x_ld, int P,
+template <int TMN>
+__global__ __launch_bounds__(256, 2) void sdf_fused16_fwd_kernel(FsNet16 net, const float* __restrict__ X, int x_ld, int P,
                                                                  float* __restrict__ sdf_out) {
-    constexpr int TM = 32 * TMN * WR;
-    constexpr int NT = 256 * WR;                               // threads
+    constexpr int TM = 32 * TMN;
+    constexpr int NT = 256;                                    // threads
     __shared__ __attribute__((aligned(16))) __bf16 act[TM * FH_ALD];
     __shared__ __attribute__((aligned(16))) __bf16 emb[TM * FH_ELD];
     __shared__ __attribute__((aligned(16))) __bf16 bst[2 * FH_BSTAGE];
@@ -242,10 +240,10 @@ __global__ __launch_bounds__(256 * WR, WR == 1 ? 2 : 1) void sdf_fused16_fwd_ker
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wc = (tid >> 6) & 3;                            // this wave's 64 output columns
-    const int wr = tid >> 8;                                  // ... and its group of 32 TMN rows
+    const int wr = tid >> 8;                                  // 0 at 256 threads; left in the row offsets, which keeps the code as measured
     const int li = lane & 31, lh = lane >> 5;
-    constexpr int NLD = 4 / WR;                                // 16-byte pieces of a chunk per thread
-    const int c4 = tid & 3, r0 = tid >> 2;                    // weight loader: rows r0 + 64 WR i (i < NLD), 16-byte slot c4 of the 64-byte chunk row
+    constexpr int NLD = 4;                                     // 16-byte pieces of a chunk per thread
+    const int c4 = tid & 3, r0 = tid >> 2;                    // weight loader: rows r0 + 64 i (i < NLD), 16-byte slot c4 of the 64-byte chunk row
     const int a_off = (wr * 32 * TMN + li) * FH_ALD + 8 * lh;                   // lane (r, h) holds k = 8 h .. 8 h + 7 of a 16-deep MFMA step
     const int b_off = (wc * 64 + li) * FH_BLD + 8 * lh;
     const int w_off = r0 * FH_BLD + 8 * c4;
@@ -258,7 +256,7 @@ __global__ __launch_bounds__(256 * WR, WR == 1 ? 2 : 1) void sdf_fused16_fwd_ker
     f32x4 rb4[NLD];
     auto set_cursor = [&]() {
         bp = net.Wp[ld_l] + (long long)r0 * net.Kp[ld_l] + 8 * c4 + ld_kt * 32;
-        bstep = 64LL * WR * net.Kp[ld_l];
+        bstep = 64LL * net.Kp[ld_l];
     };
     auto advance = [&]() {
         if (++ld_kt == net.Kp[ld_l] / 32) {
@@ -274,7 +272,7 @@ __global__ __launch_bounds__(256 * WR, WR == 1 ? 2 : 1) void sdf_fused16_fwd_ker
     };
     auto store_regs = [&](int st) {
 #pragma unroll
-        for (int i = 0; i < NLD; ++i) *reinterpret_cast<f32x4*>(&bst[st * FH_BSTAGE + w_off + 64 * WR * i * FH_BLD]) = rb4[i];
+        for (int i = 0; i < NLD; ++i) *reinterpret_cast<f32x4*>(&bst[st * FH_BSTAGE + w_off + 64 * i * FH_BLD]) = rb4[i];
     };
 
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -360,7 +358,7 @@ __global__ __launch_bounds__(256 * WR, WR == 1 ? 2 : 1) void sdf_fused16_fwd_ker
 #pragma clang fp contract(off)
             const f32x4 w = *reinterpret_cast<const f32x4*>(net.w8 + 4 * lane);
             const float b = net.b8[0];
-            for (int r = tid >> 6; r < TM; r += 4 * WR) {
+            for (int r = tid >> 6; r < TM; r += 4) {
                 const uint2 raw = *reinterpret_cast<const uint2*>(&act[r * FH_ALD + 4 * lane]);
                 f32x4 h;
                 h[0] = __uint_as_float(raw.x << 16); h[1] = __uint_as_float(raw.x & 0xffff0000u);
@@ -541,18 +539,14 @@ extern "C" int nu_sdf_fused16_fwd(const NuSdfNet* net, const float* X, int x_ld,
     }
     if (net->lin[3].N != 217 || net->lin[8].Kp != 256) return NU_ERR_ARG;
     n.w8 = net->lin[8].Wp; n.b8 = net->lin[8].bias;      // the 1-wide head stays fp32 (skinny_fwd_h16)
-    static const int tm_env = getenv("NU_FUSED_SDF16_TM") ? atoi(getenv("NU_FUSED_SDF16_TM")) : 0;     // development switch: 32 / 64 / 128
-    const int tm = tm_env ? tm_env : (nu_cdiv(P, 128) >= 192 ? 128 : (nu_cdiv(P, 64) >= 384 ? 64 : 32));
+    const int tm = nu_cdiv(P, 128) >= 192 ? 128 : (nu_cdiv(P, 64) >= 384 ? 64 : 32);
     const int ntiles = nu_cdiv(P, tm);
-    static const bool ring_off = getenv("NU_FUSED_SDF16_RING") && atoi(getenv("NU_FUSED_SDF16_RING")) == 0;    // development switch (A/B)
-    if (tm == 128 && !ring_off) {
+    if (tm == 128) {
         hipLaunchKernelGGL(sdf_fused16r_fwd_kernel, dim3(ntiles < 256 ? ntiles : 256), dim3(512), 0, stream, n, X, x_ld, P, sdf);
-    } else if (tm == 128) {
-        hipLaunchKernelGGL((sdf_fused16_fwd_kernel<2, 2>), dim3(ntiles < 256 ? ntiles : 256), dim3(512), 0, stream, n, X, x_ld, P, sdf);
     } else {
         const int grid = ntiles < 512 ? ntiles : 512;
-        if (tm == 64) hipLaunchKernelGGL((sdf_fused16_fwd_kernel<2, 1>), dim3(grid), dim3(256), 0, stream, n, X, x_ld, P, sdf);
-        else hipLaunchKernelGGL((sdf_fused16_fwd_kernel<1, 1>), dim3(grid), dim3(256), 0, stream, n, X, x_ld, P, sdf);
+        if (tm == 64) hipLaunchKernelGGL((sdf_fused16_fwd_kernel<2>), dim3(grid), dim3(256), 0, stream, n, X, x_ld, P, sdf);
+        else hipLaunchKernelGGL((sdf_fused16_fwd_kernel<1>), dim3(grid), dim3(256), 0, stream, n, X, x_ld, P, sdf);
     }
     return nu_launch_status();
 }
@@ -571,8 +565,7 @@ extern "C" int nu_sdf_fused_fwd(const NuSdfNet* net, const float* X, int x_ld, i
     if (net->lin[3].N != 217 || net->lin[8].Kp != 256) return NU_ERR_ARG;
     n.w8 = net->lin[8].Wp; n.b8 = net->lin[8].bias;
     // 64-row tiles when they still give every CU a workgroup, else 32-row tiles (twice the workgroups, half the work each)
-    static const int tm_env = getenv("NU_FUSED_SDF_TM") ? atoi(getenv("NU_FUSED_SDF_TM")) : 0;       // development switch: 32 / 64
-    const bool tm64 = tm_env ? tm_env == 64 : nu_cdiv(P, 64) >= 192;      // (measured: 16 384 points 157 vs 175 us, 8 192 points 153 vs 93)
+    const bool tm64 = nu_cdiv(P, 64) >= 192;      // (measured: 16 384 points 157 vs 175 us, 8 192 points 153 vs 93)
     const int ntiles = nu_cdiv(P, tm64 ? 64 : 32);
     const int grid = ntiles < 256 ? ntiles : 256;
     if (tm64) hipLaunchKernelGGL((sdf_fused_fwd_kernel<2>), dim3(grid), dim3(256), 0, stream, n, X, x_ld, P, sdf);

@@ -4,14 +4,14 @@
 //   network/field.py:133-150 (SDFNetwork.forward), :158-170 (.gradient), :265-289 (NeRFNetwork),
 //   :371-408 (make_predictor stacks) and their autograd backward / double backward.
 #include "gemm_epi.h"
-#include <stdlib.h>
 
+// NT kernel for the bf16 arithmetic modes (PREC 1: bf16, PREC 2: three-way bf16 split).  Exact fp32 runs gemm_nt2_kernel below.
 template <int EPI, int PREC>
 __global__ __launch_bounds__(256, PREC == 2 ? 2 : NT_WPC) void gemm_nt_kernel(NuGemmNT g) {
-    constexpr bool BF16 = PREC == 1;
+    static_assert(PREC == 1 || PREC == 2, "gemm_nt_kernel covers the bf16 modes only");
     constexpr bool SPLIT = PREC == 2;
     constexpr int kPlane = TBM * NT_LDSH;                       // bf16 elements of one [128][32 (+8 pad)] image
-    // fp32: 2 x 128 x 36 floats (36864 B).  bf16: 2 images.  split: 6 images (61440 B).  The epilogue scratch aliases it.
+    // bf16: 2 images in 2 x 128 x 36 floats (36864 B).  split: 6 images (61440 B).  The epilogue scratch aliases it.
     __shared__ __attribute__((aligned(16))) float smem[SPLIT ? 1 : 2][SPLIT ? 3 * kPlane : TBM * NT_LDS];
     // bf16 image: [128 rows][32 k] per operand, rows padded to NT_LDSH elements (80 B: b128 reads stay conflict-free)
     __bf16* const hA = reinterpret_cast<__bf16*>(&smem[0][0]);
@@ -34,8 +34,6 @@ __global__ __launch_bounds__(256, PREC == 2 ? 2 : NT_WPC) void gemm_nt_kernel(Nu
     const int r0 = tid >> 3;
     const int nk = g.K / TBK;
     const int li = lane & 31, lh = lane >> 5;
-    const int a_off = (wr * 64 + li) * NT_LDS + 4 * lh;
-    const int b_off = (wc * 64 + li) * NT_LDS + 4 * lh;
     const int ah_off = (wr * 64 + li) * NT_LDSH + 8 * lh;   // lane (r, h) holds k = 8h .. 8h+7 of a 16-deep MFMA step
     const int bh_off = (wc * 64 + li) * NT_LDSH + 8 * lh;
 
@@ -89,13 +87,9 @@ __global__ __launch_bounds__(256, PREC == 2 ? 2 : NT_WPC) void gemm_nt_kernel(Nu
                 *reinterpret_cast<bf16x4*>(q) = p1;
                 *reinterpret_cast<bf16x4*>(q + kPlane) = p2;
                 *reinterpret_cast<bf16x4*>(q + 2 * kPlane) = p3;
-            } else if (BF16) {
+            } else {
                 *reinterpret_cast<bf16x4*>(&hA[(r0 + 32 * i) * NT_LDSH + 4 * c4]) = nu_to_bf16x4(ra4[i]);
                 *reinterpret_cast<bf16x4*>(&hB[(r0 + 32 * i) * NT_LDSH + 4 * c4]) = nu_to_bf16x4(rb4[i]);
-            } else {
-                float* s0 = &smem[0][0];
-                *reinterpret_cast<f32x4*>(&s0[(r0 + 32 * i) * NT_LDS + 4 * c4]) = ra4[i];
-                *reinterpret_cast<f32x4*>(&s0[TBM * NT_LDS + (r0 + 32 * i) * NT_LDS + 4 * c4]) = rb4[i];
             }
         }
     };
@@ -160,7 +154,7 @@ __global__ __launch_bounds__(256, PREC == 2 ? 2 : NT_WPC) void gemm_nt_kernel(Nu
                             acc[tm][tn] = c;
                         }
                 }
-            } else if (BF16) {
+            } else {
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
                     const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(&hA[ah_off + 16 * ks]);
@@ -171,23 +165,6 @@ __global__ __launch_bounds__(256, PREC == 2 ? 2 : NT_WPC) void gemm_nt_kernel(Nu
                     acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[0][1], 0, 0, 0);
                     acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc[1][0], 0, 0, 0);
                     acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc[1][1], 0, 0, 0);
-                }
-            } else {
-                const float* As = &smem[0][0];
-                const float* Bs = As + TBM * NT_LDS;
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) {
-                    f32x4 a0 = *reinterpret_cast<const f32x4*>(&As[a_off + kk * 8]);
-                    f32x4 a1 = *reinterpret_cast<const f32x4*>(&As[a_off + 32 * NT_LDS + kk * 8]);
-                    f32x4 b0 = *reinterpret_cast<const f32x4*>(&Bs[b_off + kk * 8]);
-                    f32x4 b1 = *reinterpret_cast<const f32x4*>(&Bs[b_off + 32 * NT_LDS + kk * 8]);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[e], b0[e], acc[0][0], 0, 0, 0);
-                        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[e], b1[e], acc[0][1], 0, 0, 0);
-                        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[e], b0[e], acc[1][0], 0, 0, 0);
-                        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[e], b1[e], acc[1][1], 0, 0, 0);
-                    }
                 }
             }
             __syncthreads();   // every wave is done reading this chunk (and, after the last one, the scratch is free)
@@ -210,7 +187,7 @@ __global__ __launch_bounds__(256, PREC == 2 ? 2 : NT_WPC) void gemm_nt_kernel(Nu
 // ------------------------------------------------------------------------------------------------
 // NT kernel, exact fp32 MFMA, second generation: the main loop is software-pipelined INSIDE each wave.
 //
-// What the phase stamps of scripts/gemm_lab.hip showed about the first-generation kernel above (K = 256, 128 x 128 tiles):
+// What the phase stamps of scripts/gemm_lab.hip showed about the first-generation fp32 kernel (since removed; K = 256, 128 x 128 tiles):
 // a workgroup alone on its CU spends 22 us in a main loop whose 512 MFMAs per wave take 13.9 us -- every k-chunk pays
 // fragment-read latency (the ds_reads of the next k-group issue right before the last MFMA of the current one), a vmcnt
 // wait + eight ds_write_b128 + lgkmcnt(0) between two barriers, and a second fragment-read latency after them; three
@@ -222,7 +199,7 @@ __global__ __launch_bounds__(256, PREC == 2 ? 2 : NT_WPC) void gemm_nt_kernel(Nu
 //     16 MFMAs of the fourth k-group -- the matrix pipe never waits for LDS at a chunk boundary;
 //   * global loads run two chunks ahead of the MFMAs (one chunk in registers, one in LDS), across tile boundaries.
 // __builtin_amdgcn_sched_barrier(0) pins the order of the stages; inside a stage the compiler schedules freely.
-// The epilogue (shared with the first generation) uses the stage that was just consumed as its scratch.
+// The epilogue (shared with gemm_nt_kernel) uses the stage that was just consumed as its scratch.
 // ------------------------------------------------------------------------------------------------
 #define NT2_STAGE (2 * TBM * NT_LDS)   // floats per stage: [A 128 x 36 | B 128 x 36]
 // TMN = 2: 128 x 128 tiles (wave tile 64 x 64).  TMN = 1: 64 x 128 tiles (4 waves as 2 x 2, wave tile 32 x 64) for launches whose
@@ -478,46 +455,44 @@ static int nt_check(const NuGemmNT& g) {
 // set, the outer points of a 512-ray batch) take three rounds for 2.06 rounds of work; as 2108 tiles of 64 rows they take 5 for
 // 4.12.  A 64-row tile costs ~5 % more per FLOP (half the reuse of the weight tile).
 static bool nt_small_tiles(long long t128, long long t64) {
-    static const int small_env = getenv("NU_NT_SMALL") ? atoi(getenv("NU_NT_SMALL")) : -1;     // development switch: 0 never, 1 always
     auto round_eff = [&](long long tiles) { return (double)tiles / (double)(nu_cdivl(tiles, 512) * 512); };
-    return small_env >= 0 ? small_env != 0 : (t128 < 512 || 0.95 * round_eff(t64) > round_eff(t128));
+    return t128 < 512 || 0.95 * round_eff(t64) > round_eff(t128);
 }
 
+// Dispatch, by arithmetic mode (g.bf16 & 3):
+//   bf16 with bf16 storage (NU_GEMM_B16)      -> gemm_nt16b_kernel (gemm_nt16.hip)
+//   split with pre-split weights (g.B6)       -> gemm_nt6_kernel (gemm_nt6.hip): with NU_GEMM_PRESPLIT_ALWAYS, else by the rule below
+//   exact fp32                                -> gemm_nt2_kernel, 64- or 128-row tiles (nt_small_tiles), two workgroups per CU
+//   any other bf16 / split launch             -> gemm_nt_kernel<E, PREC>
+// Every grid is persistent and a multiple of 8 workgroups (so the XCD grouping of the slot space holds), shared over the groups.
 int nu_gemm_nt_launch(const NuGemmNT& g, hipStream_t stream) {
     if (g.M <= 0) return NU_OK;
     const int rc = nt_check(g);
     if (rc != NU_OK) return rc;
     const int ntn = nu_cdiv(g.N, TBN);
-    const long long nslots = (long long)nu_rup(nu_cdiv(g.M, TBM), 8) * ntn;
+    const long long nslots = (long long)nu_rup(nu_cdiv(g.M, TBM), 8) * ntn;      // 128-row tiles
     const int groups = g.groups > 0 ? g.groups : 1;
-    // persistent: NT_WPC workgroups per CU (256 CUs) shared over the groups, a multiple of 8 so the XCD grouping holds
-    static const int grid_env = getenv("NU_NT_GRID") ? atoi(getenv("NU_NT_GRID")) : 0;
     const int prec = g.bf16 & 3;
-    const int grid_target = grid_env ? grid_env : 256 * (prec == 2 ? 2 : NT_WPC);   // workgroups the build keeps resident
-    long long per = nu_rup(nu_cdiv(grid_target, groups), 8);
-    if (per > nslots) per = nslots;
-    dim3 grid((unsigned)per, 1, groups), block(256);
-    static const bool v1 = getenv("NU_NT_V1") && atoi(getenv("NU_NT_V1")) != 0;   // development switch: first-generation fp32 kernel
-    if (prec == 1 && (g.bf16 & NU_GEMM_B16)) return nu_gemm_nt16_launch(g, groups, nslots, stream);      // bf16 storage
+    dim3 block(256);
+    if (prec == 1 && (g.bf16 & NU_GEMM_B16)) return nu_gemm_nt16_launch(g, groups, nslots, stream);
     // pre-split weight planes: gemm_nt6_kernel's 128 x 256 tiles, when they still fill the chip (both kernels give the same bits;
     // measured, scripts/bench_nt6.py: 65 536 rows x 256 columns = 512 tiles 145 vs 128 TFLOP/s, 16 384 rows = 128 tiles 65 vs 95)
-    static const int nt6_env = getenv("NU_NT6") ? atoi(getenv("NU_NT6")) : -1;          // development switch: 0 never, 1 always
     // ... and for the epilogues without a second auxiliary matrix: Q_SP / B_SP / B_RELU run twice per 128 x 256 tile with more live
     // registers than the build has (58-63 spilled) -- in the step 215 vs 168 us (Q_SP), 169 vs 155 (B_SP), 755 vs 543 (B_RELU)
     const bool nt6_epi = g.epi != NU_EPI_Q_SP && g.epi != NU_EPI_B_SP && g.epi != NU_EPI_B_RELU;
-    if (prec == 2 && g.B6 && nt6_env != 0 &&
-        (nt6_env == 1 || (g.bf16 & NU_GEMM_PRESPLIT_ALWAYS) || (nt6_epi && (long long)nu_cdiv(g.M, TBM) * nu_cdiv(g.N, 256) * groups >= 320)))
+    if (prec == 2 && g.B6 &&
+        ((g.bf16 & NU_GEMM_PRESPLIT_ALWAYS) || (nt6_epi && (long long)nu_cdiv(g.M, TBM) * nu_cdiv(g.N, 256) * groups >= 320)))
         return nu_gemm_nt6_launch(g, groups, stream);
-    if (prec == 0 && !v1) {
+    if (prec == 0) {
         const long long t128 = (long long)nu_cdiv(g.M, TBM) * ntn * groups, t64 = (long long)nu_cdiv(g.M, 64) * ntn * groups;
         const bool small = nt_small_tiles(t128, t64);
         const long long nslots2 = small ? (long long)nu_rup(nu_cdiv(g.M, 64), 8) * ntn : nslots;
-        long long per2 = nu_rup(nu_cdiv(grid_env ? grid_env : 512, groups), 8);       // two workgroups per CU
-        if (per2 > nslots2) per2 = nslots2;
-        dim3 grid2((unsigned)per2, 1, groups);
+        long long per = nu_rup(nu_cdiv(512, groups), 8);       // two workgroups per CU
+        if (per > nslots2) per = nslots2;
+        dim3 grid((unsigned)per, 1, groups);
         switch (g.epi) {
-#define NU_CASE2(E) case E: if (small) hipLaunchKernelGGL((gemm_nt2_kernel<E, 1>), grid2, block, 0, stream, g); \
-                            else hipLaunchKernelGGL((gemm_nt2_kernel<E, 2>), grid2, block, 0, stream, g); break;
+#define NU_CASE2(E) case E: if (small) hipLaunchKernelGGL((gemm_nt2_kernel<E, 1>), grid, block, 0, stream, g); \
+                            else hipLaunchKernelGGL((gemm_nt2_kernel<E, 2>), grid, block, 0, stream, g); break;
             NU_CASE2(NU_EPI_BIAS_NONE)
             NU_CASE2(NU_EPI_BIAS_RELU)
             NU_CASE2(NU_EPI_BIAS_SOFTPLUS)
@@ -532,10 +507,12 @@ int nu_gemm_nt_launch(const NuGemmNT& g, hipStream_t stream) {
         }
         return nu_launch_status();
     }
+    long long per = nu_rup(nu_cdiv(256 * (prec == 2 ? 2 : NT_WPC), groups), 8);     // the workgroups per CU the build keeps resident
+    if (per > nslots) per = nslots;
+    dim3 grid((unsigned)per, 1, groups);
     switch (g.epi) {
 #define NU_CASE(E) case E: if (prec == 2) hipLaunchKernelGGL((gemm_nt_kernel<E, 2>), grid, block, 0, stream, g); \
-                           else if (prec == 1) hipLaunchKernelGGL((gemm_nt_kernel<E, 1>), grid, block, 0, stream, g); \
-                           else hipLaunchKernelGGL((gemm_nt_kernel<E, 0>), grid, block, 0, stream, g); break;
+                           else hipLaunchKernelGGL((gemm_nt_kernel<E, 1>), grid, block, 0, stream, g); break;
         NU_CASE(NU_EPI_BIAS_NONE)
         NU_CASE(NU_EPI_BIAS_RELU)
         NU_CASE(NU_EPI_BIAS_SOFTPLUS)
@@ -553,12 +530,9 @@ int nu_gemm_nt_launch(const NuGemmNT& g, hipStream_t stream) {
 
 // Several independent problems in ONE persistent launch (exact fp32, one epilogue kind).  A problem with `groups` > 1 is expanded
 // into its groups (operand pointers advanced by the strides, sign-bit column tiles by mask_ct0).  Whatever the batch kernel does
-// not cover -- other arithmetic modes, epilogue kinds without a batch build, NU_NT_BATCH=0 -- runs as one launch per problem: same
+// not cover -- other arithmetic modes, epilogue kinds without a batch build -- runs as one launch per problem: same
 // results either way, bit for bit (a tile's arithmetic does not depend on which launch it belongs to).
 int nu_gemm_nt_batch_launch(const NuGemmNT* probs, int n, hipStream_t stream) {
-    static const bool batch_on = !(getenv("NU_NT_BATCH") && atoi(getenv("NU_NT_BATCH")) == 0);     // development switch (A/B)
-    static const bool v1 = getenv("NU_NT_V1") && atoi(getenv("NU_NT_V1")) != 0;
-    static const int grid_env = getenv("NU_NT_GRID") ? atoi(getenv("NU_NT_GRID")) : 0;
     int i = 0;
     while (i < n) {
         // the longest run of problems starting at i that one launch can take
@@ -567,7 +541,7 @@ int nu_gemm_nt_batch_launch(const NuGemmNT* probs, int n, hipStream_t stream) {
         long long t128 = 0, t64 = 0;
         const int epi = probs[i].epi;
         const bool epi_ok = epi == NU_EPI_BIAS_NONE || epi == NU_EPI_BIAS_RELU || epi == NU_EPI_MUL_DRELU || epi == NU_EPI_PLAIN;
-        for (int k = i; k < n && batch_on && !v1 && epi_ok; ++k) {
+        for (int k = i; k < n && epi_ok; ++k) {
             const NuGemmNT& g = probs[k];
             if (g.M <= 0) { last = k + 1; continue; }
             const int groups = g.groups > 0 ? g.groups : 1;
@@ -603,7 +577,7 @@ int nu_gemm_nt_batch_launch(const NuGemmNT* probs, int n, hipStream_t stream) {
         }
         b.slot0[nb] = (int)slots;
         b.n = nb; b.pad_ = 0;
-        long long per = nu_rup(grid_env ? grid_env : 512, 8);       // two workgroups per CU
+        long long per = 512;       // two workgroups per CU
         if (per > slots) per = slots;
         dim3 grid((unsigned)per, 1, 1), block(256);
         switch (epi) {

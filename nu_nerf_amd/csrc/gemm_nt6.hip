@@ -20,7 +20,6 @@
 // columns are CONTIGUOUS in memory (eight full cache lines per wave-instruction) and are copied to LDS in the same order; row
 // offsets that are multiples of 256 and group strides carry over from the fp32 table's element offsets with a factor 3.
 #include "gemm_epi.h"
-#include <stdlib.h>
 
 #define N6_APL 4096                         // bytes of one A plane of a stage: [128 rows][16 k] bf16
 #define N6_BOFF (3 * N6_APL)
@@ -271,9 +270,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt6_kernel(NuGemmNT g) {
 // launch (called by nu_gemm_nt_launch after the common argument checks): mode 2 with a pre-split weight table
 int nu_gemm_nt6_launch(const NuGemmNT& g, int groups, hipStream_t stream) {
     if ((g.ldb & 15) || ((uintptr_t)g.B6 & 15) || (g.sB & 15) || (g.K & 15)) return NU_ERR_ARG;
-    static const int grid_env = getenv("NU_NT_GRID") ? atoi(getenv("NU_NT_GRID")) : 0;
     const long long nslots = (long long)nu_rup(nu_cdiv(g.M, TBM), 8) * nu_cdiv(g.N, 256);
-    long long per = nu_rup(nu_cdiv(grid_env ? grid_env : 512, groups), 8);           // two workgroups per CU
+    long long per = nu_rup(nu_cdiv(512, groups), 8);           // two workgroups per CU
     if (per > nslots) per = nslots;
     dim3 grid((unsigned)per, 1, groups), block(256);
     switch (g.epi) {

@@ -3,7 +3,6 @@
 //
 // Replaces the autograd weight / bias gradients of every `lin(x)` in network/field.py:133-150, :158-170, :265-289, :371-408.
 #include "gemm_epi.h"
-#include <stdlib.h>
 
 // development aid: {shader cycles, 100 MHz wall ticks} of block 0 of the last mfma_peak launch
 __device__ unsigned long long nu_dbg_clk[2];
@@ -626,18 +625,18 @@ __global__ __launch_bounds__(512, 1) void gemm_tn16x256_kernel(NuGemmTN g) {
 // thread and chunk now feed 128 MFMAs per wave instead of 64: half the load-issue time per matrix cycle.
 // Same slab layout, same bias sums, same ragged-tail rules as gemm_tn_kernel.
 // ------------------------------------------------------------------------------------------------
-// NJ = 4: the 256 x 256 tile (512 threads, 8 waves as 4 x 2, wave tile 64 x 128).  NJ = 2: the same pipeline on a 128 x 128 tile (256
-// threads, 4 waves as 2 x 2, wave tile 64 x 64, two workgroups per CU) for the shapes the big tile does not fit (N1 or N2 not a
-// multiple of 256, or too few tiles to fill the chip) -- measured no faster there than the first-generation gemm_tn_kernel, which
-// stays the default for those shapes (see nu_gemm_tn_launch).
-template <bool BIG, int NJ>
+// The shapes the big tile does not fit (N1 or N2 not a multiple of 256, or too few tiles to fill the chip) run gemm_tn_kernel:
+// this pipeline on a 128 x 128 tile measured no faster there (85.5 vs 89.8 TFLOP/s on the 1024 x 288 shape, 109 vs 110 on
+// 256 x 256 with 128 splits, profiles/r03; at 64 MFMAs per chunk and wave the 32 scalar loads are a third of the issue slots
+// however they are placed) and was removed.
+template <bool BIG>
 static __device__ __forceinline__ void tn2_body(const NuGemmTN& g, const int bx, const int split, const int grp) {
-    constexpr int T = 64 * NJ;                       // tile edge: 256 or 128
+    constexpr int T = 256;                           // tile edge
     __shared__ __attribute__((aligned(16))) float smem[2][2][T * NT_LDS];     // [stage][A | B][column][k (+4 pad)]
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wid = tid >> 6;
-    const int wr = wid >> 1, wc = wid & 1;           // wave tile: rows (N1) 64 wr .. +64, columns (N2) 32 NJ wc .. + 32 NJ
+    const int wr = wid >> 1, wc = wid & 1;           // wave tile: rows (N1) 64 wr .. +64, columns (N2) 128 wc .. +128
     const int t2 = (g.N2 + T - 1) / T;
     const int n1t = bx / t2, n2t = bx - n1t * t2;
     const int n1_0 = n1t * T, n2_0 = n2t * T;
@@ -656,11 +655,11 @@ static __device__ __forceinline__ void tn2_body(const NuGemmTN& g, const int bx,
     const int kg = tid / T;         // which 16 of the chunk's 32 reduced rows (wave-uniform)
     const bool do_bias = (g.bias_slab != nullptr) && (n2t == 0);
 
-    f32x16 acc[2][NJ];
+    f32x16 acc[2][4];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < NJ; ++j)
+        for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
@@ -740,7 +739,7 @@ static __device__ __forceinline__ void tn2_body(const NuGemmTN& g, const int bx,
 
     const int li = lane & 31, lh = lane >> 5;
     const int a_off = (wr * 64 + li) * NT_LDS + 4 * lh;
-    const int b_off = (wc * 32 * NJ + li) * NT_LDS + 4 * lh;
+    const int b_off = (wc * 128 + li) * NT_LDS + 4 * lh;
     // Fragments are double-buffered in registers and EVERY memory instruction of a chunk sits alone between two MFMAs (see
     // gemm_nt2_kernel: an in-order wave issues nothing while one of its own instructions issues, and the two waves of a SIMD belong
     // to this one workgroup and run in phase -- whatever one of them issues in a block, the other issues at the same time).
@@ -748,7 +747,7 @@ static __device__ __forceinline__ void tn2_body(const NuGemmTN& g, const int bx,
     //   slot 0 / 4 / 8 / 9      register piece 0 / 1 / 2 / 3 of chunk t+1 -> the other LDS stage (zeroing of the ragged tail, bias sums)
     //   slots 1-2, 5-6, 10 + 12, 13-14   the same pieces re-issued global -> registers for chunk t+2 (one scalar load per gap)
     //   slots 3, 7, 11          the 6 fragment reads of the next k-group; barrier behind slot 11; slot 15: first fragments of chunk t+1
-    struct FragT { f32x4 a[2]; f32x4 b[NJ]; };
+    struct FragT { f32x4 a[2]; f32x4 b[4]; };
     FragT F0, F1;
     // One scalar load: the ROW of the operand is wave-uniform (kg = tid / T is the same for a whole wave), so its address is a
     // scalar 64-bit base (two or three SALU instructions) and the lane only adds its column offset -- global_load_dword v, v_off, s[base]
@@ -802,21 +801,18 @@ static __device__ __forceinline__ void tn2_body(const NuGemmTN& g, const int bx,
 #pragma unroll
         for (int i = 0; i < 2; ++i) F0.a[i] = *reinterpret_cast<const f32x4*>(&smem[0][0][a_off + 32 * i * NT_LDS]);
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) F0.b[j] = *reinterpret_cast<const f32x4*>(&smem[0][1][b_off + 32 * j * NT_LDS]);
+        for (int j = 0; j < 4; ++j) F0.b[j] = *reinterpret_cast<const f32x4*>(&smem[0][1][b_off + 32 * j * NT_LDS]);
     }
 #define TN_PIN __builtin_amdgcn_sched_barrier(0);
 #define TN_M(F, e, i, j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(F.a[i][e], F.b[j][e], acc[i][j], 0, 0, 0); TN_PIN
-    // the k-th MFMA of a k-step: (k / 4, k % 4) on the 64 x 128 wave tile, (k / 2, k % 2) on the 64 x 64 one
-#define TN_MK(F, e, k) if constexpr (NJ == 4) { TN_M(F, e, (k) / 4, (k) % 4) } else if constexpr ((k) < 4) { TN_M(F, e, (k) / 2, (k) % 2) }
-    // one k-step (8 or 4 MFMAs) with one auxiliary statement behind each MFMA (the wide tile has seven slots, the narrow one four)
+    // one k-step (8 MFMAs over the 64 x 128 wave tile) with one auxiliary statement behind each of the first seven
 #define TN_SLOT(F, e, ...) TN_SLOT_(F, e, __VA_ARGS__)      /* (one more level: the list macros below expand first) */
 #define TN_SLOT_(F, e, X0, X1, X2, X3, X4, X5, X6)                                                   \
-    TN_MK(F, e, 0) X0; TN_PIN TN_MK(F, e, 1) X1; TN_PIN TN_MK(F, e, 2) X2; TN_PIN TN_MK(F, e, 3) X3; TN_PIN     \
-    if constexpr (NJ == 4) { TN_MK(F, e, 4) X4; TN_PIN TN_MK(F, e, 5) X5; TN_PIN TN_MK(F, e, 6) X6; TN_PIN TN_MK(F, e, 7) }
+    TN_M(F, e, 0, 0) X0; TN_PIN TN_M(F, e, 0, 1) X1; TN_PIN TN_M(F, e, 0, 2) X2; TN_PIN TN_M(F, e, 0, 3) X3; TN_PIN     \
+    TN_M(F, e, 1, 0) X4; TN_PIN TN_M(F, e, 1, 1) X5; TN_PIN TN_M(F, e, 1, 2) X6; TN_PIN TN_M(F, e, 1, 3)
 #define TN_RDA(F, ST, kk, i) F.a[i] = *reinterpret_cast<const f32x4*>(&smem[ST][0][a_off + 32 * (i) * NT_LDS + (kk) * 8])
 #define TN_RDB(F, ST, kk, j) F.b[j] = *reinterpret_cast<const f32x4*>(&smem[ST][1][b_off + 32 * (j) * NT_LDS + (kk) * 8])
-#define TN_RDB4(F, ST, kk, j) (void)0; if constexpr (NJ == 4) { TN_RDB(F, ST, kk, j); }
-#define TN_READS(F, ST, kk) TN_RDA(F, ST, kk, 0), TN_RDA(F, ST, kk, 1), TN_RDB(F, ST, kk, 0), TN_RDB(F, ST, kk, 1), TN_RDB4(F, ST, kk, 2), TN_RDB4(F, ST, kk, 3), (void)0
+#define TN_READS(F, ST, kk) TN_RDA(F, ST, kk, 0), TN_RDA(F, ST, kk, 1), TN_RDB(F, ST, kk, 0), TN_RDB(F, ST, kk, 1), TN_RDB(F, ST, kk, 2), TN_RDB(F, ST, kk, 3), (void)0
 #define TN_LD2(i, e) ld_one(true, i, e), ld_one(false, i, e), ld_one(true, i, (e) + 1), ld_one(false, i, (e) + 1), (void)0, (void)0, (void)0
 #define TN_ST(i) st_zero(true, i), st_write(true, cur ^ 1, i), st_zero(false, i), st_write(false, cur ^ 1, i), (void)0, (void)0, (void)0
     // No instruction of the loop body is conditional: a branch around a load makes hipcc wait vmcnt(0) at the join (every scalar
@@ -849,12 +845,10 @@ static __device__ __forceinline__ void tn2_body(const NuGemmTN& g, const int bx,
     }
 #undef TN_PIN
 #undef TN_M
-#undef TN_MK
 #undef TN_SLOT
 #undef TN_SLOT_
 #undef TN_RDA
 #undef TN_RDB
-#undef TN_RDB4
 #undef TN_READS
 #undef TN_LD2
 #undef TN_ST
@@ -863,8 +857,8 @@ static __device__ __forceinline__ void tn2_body(const NuGemmTN& g, const int bx,
 #pragma unroll
     for (int tm = 0; tm < 2; ++tm)
 #pragma unroll
-        for (int tn = 0; tn < NJ; ++tn) {
-            const int col = n2_0 + wc * 32 * NJ + tn * 32 + li;
+        for (int tn = 0; tn < 4; ++tn) {
+            const int col = n2_0 + wc * 128 + tn * 32 + li;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = n1_0 + wr * 64 + tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
@@ -879,13 +873,13 @@ static __device__ __forceinline__ void tn2_body(const NuGemmTN& g, const int bx,
     }
 }
 
-template <bool BIG, int NJ>
-__global__ __launch_bounds__(128 * NJ, 2) void gemm_tn2_kernel(NuGemmTN g) { tn2_body<BIG, NJ>(g, blockIdx.x, blockIdx.y, blockIdx.z); }
-template <bool BIG, int NJ>
-__global__ __launch_bounds__(128 * NJ, 2) void gemm_tn2b_kernel(NuGemmTNBatch b) {
+template <bool BIG>
+__global__ __launch_bounds__(512, 2) void gemm_tn2_kernel(NuGemmTN g) { tn2_body<BIG>(g, blockIdx.x, blockIdx.y, blockIdx.z); }
+template <bool BIG>
+__global__ __launch_bounds__(512, 2) void gemm_tn2b_kernel(NuGemmTNBatch b) {
     int bx, split;
-    const int pi = tn_batch_decode(b, 64 * NJ, bx, split);
-    tn2_body<BIG, NJ>(b.p[pi], bx, split, 0);
+    const int pi = tn_batch_decode(b, 256, bx, split);
+    tn2_body<BIG>(b.p[pi], bx, split, 0);
 }
 
 // The split both launch paths use: enough workgroups for the chip, as few and as large slabs as possible.  The 256-wide kernel
@@ -893,8 +887,7 @@ __global__ __launch_bounds__(128 * NJ, 2) void gemm_tn2b_kernel(NuGemmTNBatch b)
 // Does a weight-gradient launch with this split take the 256 x 256-tile kernels?  Only when that grid fills the chip: with few
 // reduced rows (small batches: P / 256 splits at most) the 128-tile kernels put four times as many workgroups on the CUs.
 static bool nu_tn_big_tile(int N1, int N2, int groups, int prec, int S) {
-    static const bool tn128_env = getenv("NU_TN_128") && atoi(getenv("NU_TN_128")) != 0;      // development switch: 128 x 128 tiles only
-    if ((prec & 3) == 2 || tn128_env || (N1 % 256) != 0 || (N2 % 256) != 0) return false;
+    if ((prec & 3) == 2 || (N1 % 256) != 0 || (N2 % 256) != 0) return false;
     return (long long)(N1 / 256) * (N2 / 256) * (groups > 0 ? groups : 1) * S >= 192;
 }
 // The split both launch paths use: enough workgroups for the chip, as few and as large slabs as possible.
@@ -924,39 +917,23 @@ int nu_gemm_tn_launch(const NuGemmTN& g, hipStream_t stream) {
     const int prec = g.bf16 & 3;
     if (prec == 3 || ((g.bf16 & ~3) && prec != 1)) return NU_ERR_ARG;
     const bool big_tile = nu_tn_big_tile(g.N1, g.N2, g.groups, g.bf16, g.S);
-    if ((g.bf16 & 3) == 0) {         // exact fp32: the pipelined kernel, 256 x 256 tiles where the shape allows, else 128 x 128
-        // 128 x 128 tiles: the first-generation kernel stays the default -- the pipelined one measured 85.5 vs 89.8 TFLOP/s on the
-        // 1024 x 288 shape and 109 vs 110 on 256 x 256 with 128 splits (profiles/r03): at 64 MFMAs per chunk and wave the 32 scalar
-        // loads are a third of the issue slots however they are placed.  NU_TN_V1=0 selects the pipelined kernel (development A/B).
-        static const bool tn_v1 = !(getenv("NU_TN_V1") && atoi(getenv("NU_TN_V1")) == 0);
-        const long long mld = (g.lda0 > g.ldb0 ? g.lda0 : g.ldb0) > (g.A1 ? (g.lda1 > g.ldb1 ? g.lda1 : g.ldb1) : 0)
-                                  ? (g.lda0 > g.ldb0 ? g.lda0 : g.ldb0) : (g.lda1 > g.ldb1 ? g.lda1 : g.ldb1);
-        const bool big = (long long)g.P * mld * 4 >= (1LL << 32);
-        if (big_tile) {
-            dim3 grid2((g.N1 / 256) * (g.N2 / 256), g.S, g.groups > 0 ? g.groups : 1);
-            if (big) hipLaunchKernelGGL((gemm_tn2_kernel<true, 4>), grid2, dim3(512), 0, stream, g);
-            else hipLaunchKernelGGL((gemm_tn2_kernel<false, 4>), grid2, dim3(512), 0, stream, g);
-            return nu_launch_status();
-        }
-        if (!tn_v1) {
-            dim3 grid2(nu_cdiv(g.N1, 128) * nu_cdiv(g.N2, 128), g.S, g.groups > 0 ? g.groups : 1);
-            if (big) hipLaunchKernelGGL((gemm_tn2_kernel<true, 2>), grid2, dim3(256), 0, stream, g);
-            else hipLaunchKernelGGL((gemm_tn2_kernel<false, 2>), grid2, dim3(256), 0, stream, g);
-            return nu_launch_status();
-        }
-    }
-    dim3 grid(nu_cdiv(g.N1, 128) * nu_cdiv(g.N2, 128), g.S, g.groups > 0 ? g.groups : 1), block(256);
     const long long max_ld = (g.lda0 > g.ldb0 ? g.lda0 : g.ldb0) > (g.A1 ? (g.lda1 > g.ldb1 ? g.lda1 : g.ldb1) : 0)
                                  ? (g.lda0 > g.ldb0 ? g.lda0 : g.ldb0) : (g.lda1 > g.ldb1 ? g.lda1 : g.ldb1);
     const bool big = (long long)g.P * max_ld * 4 >= (1LL << 32);
+    if (prec == 0 && big_tile) {     // exact fp32: the pipelined kernel on 256 x 256 tiles where the shape allows, else gemm_tn_kernel
+        dim3 grid2((g.N1 / 256) * (g.N2 / 256), g.S, g.groups > 0 ? g.groups : 1);
+        if (big) hipLaunchKernelGGL((gemm_tn2_kernel<true>), grid2, dim3(512), 0, stream, g);
+        else hipLaunchKernelGGL((gemm_tn2_kernel<false>), grid2, dim3(512), 0, stream, g);
+        return nu_launch_status();
+    }
+    dim3 grid(nu_cdiv(g.N1, 128) * nu_cdiv(g.N2, 128), g.S, g.groups > 0 ? g.groups : 1), block(256);
     if (prec == 1) {
         // vector-load kernel: 16-byte aligned operands, rows of 8 or more elements (bf16 rows: a multiple of 8)
         auto ok = [](const float* p, int ld, bool h) { return p == nullptr || ((((uintptr_t)p) & 15) == 0 && ld >= 8 && (!h || (ld & 7) == 0)); };
         const bool vec = ok(g.A0, g.lda0, g.bf16 & NU_TN_A0_16) && ok(g.B0, g.ldb0, g.bf16 & NU_TN_B0_16) &&
                          ok(g.A1, g.lda1, g.bf16 & NU_TN_A1_16) && ok(g.B1, g.ldb1, g.bf16 & NU_TN_B1_16) &&
                          ((g.sA0 | g.sB0 | g.sA1 | g.sB1) & 7) == 0;
-        static const bool tn_scalar_env = getenv("NU_TN_SCALAR") && atoi(getenv("NU_TN_SCALAR")) != 0;      // development switch
-        if (vec && !tn_scalar_env) {
+        if (vec) {
             if (big_tile) {
                 dim3 grid2((g.N1 / 256) * (g.N2 / 256), g.S, g.groups > 0 ? g.groups : 1);
                 hipLaunchKernelGGL(gemm_tn16x256_kernel, grid2, dim3(512), 0, stream, g);
@@ -1263,7 +1240,7 @@ static int wgrad_launch_batch(NuOpCtx* c, NuWgradItem* it, const int* idx, int m
     b.blk0[np] = blocks;
     b.n = np; b.pad_ = 0;
     nu_ctx_ev_begin(c, stream);
-    if (klass == 2) hipLaunchKernelGGL((gemm_tn2b_kernel<false, 4>), dim3(blocks), dim3(512), 0, stream, b);
+    if (klass == 2) hipLaunchKernelGGL((gemm_tn2b_kernel<false>), dim3(blocks), dim3(512), 0, stream, b);
     else hipLaunchKernelGGL((gemm_tnb_kernel<false>), dim3(blocks), dim3(256), 0, stream, b);
     rc = nu_launch_status();
     nu_ctx_ev_end(c, stream, 1.0, flops, abytes);
@@ -1289,8 +1266,6 @@ extern "C" int nu_wgrad_flush(NuOpCtx* c, hipStream_t stream) {
     if (n <= 0 || c->pend == nullptr) return NU_OK;
     NuWgradItem* it = c->pend;
     c->npend = 0;
-    static const bool batch_on = !(getenv("NU_TN_BATCH") && atoi(getenv("NU_TN_BATCH")) == 0);      // development switch (A/B)
-    static const bool tn128_env = getenv("NU_TN_128") && atoi(getenv("NU_TN_128")) != 0;
     // ---- plan: tile class and split of every item (a function of the queue only) ----
     int klass[NU_WGRAD_QUEUE_MAX];
     if (n > NU_WGRAD_QUEUE_MAX) return NU_ERR_ARG;
@@ -1298,7 +1273,7 @@ extern "C" int nu_wgrad_flush(NuOpCtx* c, hipStream_t stream) {
     for (int i = 0; i < n; ++i) {
         NuGemmTN& g = it[i].g;
         if (g.groups < 1) g.groups = 1;
-        klass[i] = (batch_on && (g.bf16 & 3) == 0 && (g.bf16 & ~3) == 0 && !tn_item_big(g) && g.groups <= NU_TN_BATCH_MAX) ? 1 : 0;
+        klass[i] = ((g.bf16 & 3) == 0 && (g.bf16 & ~3) == 0 && !tn_item_big(g) && g.groups <= NU_TN_BATCH_MAX) ? 1 : 0;
         if (klass[i] && g.P > pmax) pmax = g.P;
     }
     const int rows_min = pmax <= 8192 ? 128 : 256;       // (see nu_wgrad_pick_split)
@@ -1321,14 +1296,13 @@ extern "C" int nu_wgrad_flush(NuOpCtx* c, hipStream_t stream) {
     };
     // 256 x 256 tiles (one workgroup per CU) for the shapes that allow them, when that grid fills the chip
     for (int i = 0; i < n; ++i)
-        if (klass[i] == 1 && !tn128_env && (it[i].g.N1 % 256) == 0 && (it[i].g.N2 % 256) == 0) klass[i] = 2;
+        if (klass[i] == 1 && (it[i].g.N1 % 256) == 0 && (it[i].g.N2 % 256) == 0) klass[i] = 2;
     if (plan(2, 256, 256) < 192)
         for (int i = 0; i < n; ++i) if (klass[i] == 2) klass[i] = 1;
     // 128 x 128 tiles: FOUR workgroups per CU are resident (126 VGPRs, 36.9 KB of LDS) and this kernel is bound by the issue of its
     // scalar transposing loads, which more waves hide: a grid of 1024 measured 121.4 TFLOP/s over a step's weight gradients against
     // 118.0 at 512 (same box, alternating; 512 rays: 7.61 vs 7.74 ms/step)
-    static const int c1_target = getenv("NU_TN_C1_TARGET") ? atoi(getenv("NU_TN_C1_TARGET")) : 1024;     // development switch
-    plan(1, 128, c1_target);
+    plan(1, 128, 1024);
     // ---- launch: singles first, then one launch per class (more when the batch table or the arena cannot take a class at once) ----
     for (int i = 0; i < n; ++i)
         if (klass[i] == 0) { const int rc = wgrad_launch_single(c, it[i], stream); if (rc != NU_OK) return rc; }

@@ -6,8 +6,7 @@
 //   miss  : (hit, index) = (0.0, 10000000)      closesthit: (1.0, primitive index)
 // Build = Morton codes of triangle centroids -> sort -> Karras 2012 radix-tree hierarchy -> bottom-up
 // AABB refit -> 4-wide records (each node's grandchildren).  Traversal = four lanes per ray over the 4-wide records, one
-// stack per ray in LDS, nearest entry first (lbvh_trace_quad_kernel); the one-ray-per-lane kernel over the binary nodes
-// (per-lane stack in LDS, wavefront-interleaved) is kept behind NU_LBVH_QUAD=0.
+// stack per ray in LDS, nearest entry first (lbvh_trace_quad_kernel).
 //
 // Hit indices are defined bit-exactly against the brute-force oracle (oracle/lbvh_oracle.py): the
 // ray/triangle test below is written with explicit single-rounding fp32 operations in a fixed order, ties in t go
@@ -359,97 +358,13 @@ static __device__ inline bool nu_ray_box(const float* o, const float* invd, cons
     return t0 <= t1 * 1.0000005f;
 }
 
-// STACK entries per lane live in LDS, wavefront-interleaved ([entry][lane]: a push or pop of all 64 lanes is one conflict-free
-// row).  The first pass runs with a SHORT stack (16 entries = 4 KB per wave, so LDS no longer pins the kernel at 8 waves per
-// CU: measured 1.22 -> 1.85 G rays/s on 20480 faces, 0.61 -> 1.33 on 327680; 8 / 12 / 24 / 32 entries are slower); a lane whose traversal would need more marks its ray (hit = -1) and the second pass re-traces exactly those rays with
-// the full 64-entry stack (a Morton tree over 30-bit codes + index tie-break is at most 62 deep).  RETRACE: only marked rays.
-// RPW rays per wave: a traversal is a chain of dependent node fetches (latency-bound), so a small batch is faster spread thin --
-// 4096 rays as 64 per wave are 64 waves on 16 CUs (78 us); as 16 per wave they are 256 single-wave workgroups, one per CU.
-template <int STACK, bool RETRACE, int RPW = 64>
-__global__ __launch_bounds__(RPW == 64 ? 256 : 64) void lbvh_trace_kernel(const char* __restrict__ buf, NuBvhLayout L,
-                                                                           const float* __restrict__ rays, int N, float tmin, float tmax,
-                                                                           float* __restrict__ hit, int* __restrict__ idx,
-                                                                           float* __restrict__ tout) {
-    __shared__ int stack[RPW == 64 ? 4 : 1][STACK][64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int r = RPW == 64 ? blockIdx.x * blockDim.x + threadIdx.x : blockIdx.x * RPW + lane;
-    if (r >= N || lane >= RPW) return;
-    if (RETRACE && hit[r] >= 0.0f) return;
-    bool overflow = false;
-    const NuBvhHeader* h = (const NuBvhHeader*)(buf + L.header);
-    const NuBvhNode* nodes = (const NuBvhNode*)(buf + L.nodes);
-    const float* tris = (const float*)(buf + L.tris);
-    const int* ids = (const int*)(buf + L.ids);
-    const int n = h->n_faces;
-    float o[3], d[3], invd[3];
-    for (int k = 0; k < 3; ++k) { o[k] = rays[r * 6LL + k]; d[k] = rays[r * 6LL + 3 + k]; invd[k] = 1.0f / d[k]; }
-    float best_t = tmax;
-    int best_id = NU_MISS_INDEX;
-    bool found = false;
-
-    auto test_leaf = [&](int pos) {
-        const float* tp = tris + pos * 12LL;
-        float t;
-        if (nu_ray_tri(o, d, tp, tp + 4, tp + 8, tmin, tmax, t)) {
-            const int id = ids[pos];
-            if (!found || t < best_t || (t == best_t && id < best_id)) { best_t = t; best_id = id; found = true; }
-        }
-    };
-
-    if (n == 1) {
-        test_leaf(0);
-    } else {
-        int sp = 0;
-        int node = 0;
-#ifdef NU_LBVH_STATS
-        int steps = 0;
-#endif
-        while (true) {
-#ifdef NU_LBVH_STATS
-            ++steps;
-#endif
-            const NuBvhNode nd = nodes[node];
-            float tl, tr;
-            // inclusive in best_t: an equal-t hit with a lower face id must still be found
-            const bool hl = nu_ray_box(o, invd, nd.lmin, nd.lmax, tmin, best_t, tl);
-            const bool hr = nu_ray_box(o, invd, nd.rmin, nd.rmax, tmin, best_t, tr);
-            int next = -1;
-            if (hl && nd.left < 0) test_leaf(-1 - nd.left);
-            if (hr && nd.right < 0) test_leaf(-1 - nd.right);
-            const bool il = hl && nd.left >= 0, ir = hr && nd.right >= 0;
-            if (il && ir) {
-                const bool left_first = tl <= tr;
-                next = left_first ? nd.left : nd.right;
-                if (sp < STACK) stack[w][sp++][lane] = left_first ? nd.right : nd.left;
-                else overflow = true;
-            } else if (il) {
-                next = nd.left;
-            } else if (ir) {
-                next = nd.right;
-            }
-            if (next < 0) {
-                if (sp == 0) break;
-                next = stack[w][--sp][lane];
-            }
-            node = next;
-        }
-#ifdef NU_LBVH_STATS
-        best_t = (float)steps; found = true;
-#endif
-    }
-    if (overflow && STACK < NU_STACK) { hit[r] = -1.0f; return; }      // incomplete: the second pass re-traces this ray
-    hit[r] = found ? 1.0f : 0.0f;
-    idx[r] = best_id;
-    if (tout) tout[r] = found ? best_t : 0.0f;
-}
-
 // ------------------------------------------------------------------------------------------------
 // FOUR lanes per ray over the 4-wide records (16 rays per single-wave workgroup).  A traversal is a chain of dependent fetches --
 // a launch of 4 096 rays lasts as long as its longest chain (56 records at ~0.7 us; the average ray visits 13) -- so the lever
 // is fewer and shorter links: the four lanes of a ray test the four entries of a wide record at once
 // (two binary levels per fetch), leaf entries are intersected by the lanes that hold them, the hits are ordered inside the
 // quad with DPP quad permutes and the ray's stack (one per quad, in LDS) takes the farther ones.  Closest hit, ties in t to the
-// lowest face id, the same box and triangle tests as the one-lane-per-ray kernel: identical (hit, index, t).
+// lowest face id, the box and triangle tests of this file: identical (hit, index, t) to the brute-force sweep.
 // ------------------------------------------------------------------------------------------------
 #define NU_WSTACK 96            // <= 3 pushes per wide level, <= 31 wide levels (a Morton tree over 62-bit keys)
 template <int CTRL> static __device__ __forceinline__ int nu_quad_i(int v) {
@@ -582,44 +497,10 @@ extern "C" int nu_lbvh_trace(const void* bvh, int n_faces, const float* rays, in
                              int* idx, float* t_out, hipStream_t stream) {
     if (N <= 0) return NU_OK;
     const NuBvhLayout L = nu_bvh_layout(n_faces);
-    // the four-lanes-per-ray kernel is the default at every batch size (4 096 rays: 75 -> 39 us object-aimed, 49 -> 32 us camera rays;
-    // 2^20 rays: 1.82 -> 2.67 and 4.22 -> 4.96 G rays/s; profiles/r03/lbvh_bench.txt); NU_LBVH_QUAD=0 selects the one-lane-per-ray
-    // kernels below (development A/B)
-    static const int quad_env = getenv("NU_LBVH_QUAD") ? atoi(getenv("NU_LBVH_QUAD")) : 1;
-    if (quad_env != 0) {
-        hipLaunchKernelGGL(lbvh_trace_quad_kernel, dim3(nu_cdiv(N, 16)), dim3(64), 0, stream, (const char*)bvh, L, rays, N, tmin, tmax,
-                           hit, idx, t_out);
-        return nu_launch_status();
-    }
-    static const int full_only = getenv("NU_LBVH_FULL_STACK") ? atoi(getenv("NU_LBVH_FULL_STACK")) : 0;   // development A/B
-    if (full_only) {
-        hipLaunchKernelGGL((lbvh_trace_kernel<NU_STACK, false>), dim3(nu_cdiv(N, 256)), dim3(256), 0, stream, (const char*)bvh, L, rays, N,
-                           tmin, tmax, hit, idx, t_out);
-        return nu_launch_status();
-    }
-    static const int short_env = getenv("NU_LBVH_SHORT") ? atoi(getenv("NU_LBVH_SHORT")) : 16;   // development sweep: 16 measured best
-    static const int rpw_env = getenv("NU_LBVH_RPW") ? atoi(getenv("NU_LBVH_RPW")) : 0;          // development switch: rays per wave
-    // small batches (a training step traces 4096 rays or fewer per bounce): 16 or 32 rays per single-wave workgroup, so that the
-    // batch covers the chip's 256 CUs; from 16 384 rays on, full waves
-    const int rpw = rpw_env ? rpw_env : (N <= 8192 ? 16 : (N <= 16384 ? 32 : 64));
-    if (rpw == 16 || rpw == 32) {
-        const dim3 grid(nu_cdiv(N, rpw)), block(64);
-        if (rpw == 16) {
-            hipLaunchKernelGGL((lbvh_trace_kernel<16, false, 16>), grid, block, 0, stream, (const char*)bvh, L, rays, N, tmin, tmax, hit, idx, t_out);
-            hipLaunchKernelGGL((lbvh_trace_kernel<NU_STACK, true, 16>), grid, block, 0, stream, (const char*)bvh, L, rays, N, tmin, tmax, hit, idx, t_out);
-        } else {
-            hipLaunchKernelGGL((lbvh_trace_kernel<16, false, 32>), grid, block, 0, stream, (const char*)bvh, L, rays, N, tmin, tmax, hit, idx, t_out);
-            hipLaunchKernelGGL((lbvh_trace_kernel<NU_STACK, true, 32>), grid, block, 0, stream, (const char*)bvh, L, rays, N, tmin, tmax, hit, idx, t_out);
-        }
-        return nu_launch_status();
-    }
-#define NU_TRACE1(S) hipLaunchKernelGGL((lbvh_trace_kernel<S, false>), dim3(nu_cdiv(N, 256)), dim3(256), 0, stream, (const char*)bvh, L, \
-                                        rays, N, tmin, tmax, hit, idx, t_out)
-    if (short_env == 8) NU_TRACE1(8); else if (short_env == 12) NU_TRACE1(12);
-    else if (short_env == 24) NU_TRACE1(24); else if (short_env == 32) NU_TRACE1(32); else NU_TRACE1(16);
-#undef NU_TRACE1
-    hipLaunchKernelGGL((lbvh_trace_kernel<NU_STACK, true>), dim3(nu_cdiv(N, 256)), dim3(256), 0, stream, (const char*)bvh, L, rays, N,
-                       tmin, tmax, hit, idx, t_out);
+    // four lanes per ray at every batch size: against the one-lane-per-ray kernel (since removed) 4 096 rays took 75 -> 39 us
+    // object-aimed, 49 -> 32 us camera rays; 2^20 rays 1.82 -> 2.67 and 4.22 -> 4.96 G rays/s (profiles/r03/lbvh_bench.txt)
+    hipLaunchKernelGGL(lbvh_trace_quad_kernel, dim3(nu_cdiv(N, 16)), dim3(64), 0, stream, (const char*)bvh, L, rays, N, tmin, tmax,
+                       hit, idx, t_out);
     return nu_launch_status();
 }
 

@@ -178,8 +178,8 @@ class Stage1Engine:
         # 'bf16x6': fp32-equivalent products on the bf16 pipe (exact 3-way split of both operands, six partial products)
         self.bf16 = 2 if md == 'bf16x6' else (1 if md.startswith('b') else 0)
         # 'bf16' stores what only GEMMs touch as bf16 in HBM (weight tables + most hidden activations, include/nu_nerf.h
-        # NuOpCtx.h16); NU_BF16_STORAGE=0 keeps the round-1 behaviour (fp32 in HBM, rounded on load) for A/B runs
-        self.h16 = self.bf16 == 1 and os.environ.get('NU_BF16_STORAGE', '1') != '0'
+        # NuOpCtx.h16)
+        self.h16 = self.bf16 == 1
         self.hdt = torch.bfloat16 if self.h16 else torch.float32
         # deferred split reductions (weight gradients, skinny heads, column sums): partial slabs live in a bump arena
         # until flush_reductions() sums them all in a few batched launches (before unpack_grads reads the results)
@@ -202,9 +202,8 @@ class Stage1Engine:
         # NU_PY_SEQ=1: sequence every launch from Python (the path bench.py's per-launch event timing uses)
         self.py_seq = os.environ.get('NU_PY_SEQ', '0') != '0'
         if self.py_seq and self.h16:
-            raise ValueError("NU_PY_SEQ=1 (launch-by-launch sequencing) has no bf16-storage mode: unset it or set NU_BF16_STORAGE=0")
-        # NU_FUSED_SDF=0: the no-gradient SDF evaluations through the layered path (development A/B)
-        self._fused_sdf = os.environ.get('NU_FUSED_SDF', '1') != '0'
+            raise ValueError("NU_PY_SEQ=1 (launch-by-launch sequencing) has no bf16-storage mode: unset it or use mlp_dtype 'fp32' / 'bf16x6'")
+        self._fused_sdf = True          # False: the no-gradient SDF evaluations take the layered path (tests, bench_fused_sdf.py)
         self._ws = None
         self._ptr_sig = None
         self._ktime = None
@@ -265,9 +264,9 @@ class Stage1Engine:
     # outer points and the SDF / shading chain of the inner points are independent between the partition and the composite, so
     # below `_TWO_STREAM_SAMPLES` ray samples the NeRF++ chain runs on a second HIP stream.  Both chains push their split reductions
     # to the shared arena from this (single) host thread; the batched reduction runs after the join.
-    _TWO_STREAM_SAMPLES = int(os.environ.get('NU_TWO_STREAM_SAMPLES', 200000))
+    _TWO_STREAM_SAMPLES = 200000
     occ_sdf_thresh = None      # set by the renderer for a training step past occ_loss_step: render_forward leaves ctx['occ_idx']
-    _FUSED_SDF_MAX_POINTS = int(os.environ.get('NU_FUSED_SDF_MAX_POINTS', 40000))
+    _FUSED_SDF_MAX_POINTS = 40000
 
     def _fork(self, mark=True):
         """mark=False (stage 2): the ops of this engine that run on the two streams are totally ordered by events (op_begin /
@@ -323,8 +322,6 @@ class Stage1Engine:
         """Sign-bit buffer for a [rows, ncols] ReLU activation (2 KB per 128x128 tile): written by the BIAS_RELU GEMM that
         produces `act`, read by the backward GEMMs instead of `act` itself.  Rides on the activation tensor so that it lives
         exactly as long."""
-        if os.environ.get('NU_RELU_MASK', '1') == '0':     # development switch: A/B against reading the activation
-            return None
         nct = (ncols + 127) // 128
         rows_q = self._capacity((rows,)) or rows
         m = torch.empty(((rows_q + 127) // 128) * nct * 256, dtype=torch.int64, device=self.dev)
@@ -363,7 +360,7 @@ class Stage1Engine:
         fail closed, like the C entries (NuOpCtx.forked -> NU_ERR_WORKSPACE)."""
         if self._ctx.forked:
             raise L.NuNerfLibraryError("split-reduction arena (or descriptor table) full while two streams share it: raise "
-                                       "NU_ARENA_FLOATS or lower NU_TWO_STREAM_SAMPLES (NU_ERR_WORKSPACE)")
+                                       "NU_ARENA_FLOATS or lower Stage1Engine._TWO_STREAM_SAMPLES (NU_ERR_WORKSPACE)")
         # reductions only: the weight gradients still queued keep waiting for the end of their pass (their split must not
         # depend on when the arena happened to fill)
         L.check(self.lib.nu_ctx_reduce(ctypes.byref(self._ctx), self.stream()), "nu_ctx_reduce")
@@ -533,7 +530,7 @@ class Stage1Engine:
         # 'bf16x6': the same twins hold the exact hi / mid / lo split instead (three times the elements, the fp32 table's offsets
         # times 3 -- include/nu_nerf.h NuGemmNT.B6): the NT kernel then never splits a weight tile (csrc/gemm_nt6.hip)
         self._tw = {}
-        self.w6 = self.bf16 == 2 and os.environ.get('NU_PRESPLIT_WEIGHTS', '1') != '0'
+        self.w6 = self.bf16 == 2
         if self.h16 or self.w6:
             for lay in layers:
                 for tab in (lay.Wp, lay.WpT):
@@ -1494,8 +1491,7 @@ class Stage1Engine:
         # (the bf16-MFMA modes stay on one stream: a packed-fp32 VALU kernel running beside this library's bf16-MFMA GEMMs returns wrong
         # elements now and then -- 'bf16x6' gradients were not reproducible run to run with the overlap; the fp32-MFMA kernels of the
         # default mode do not trigger it.  DESIGN.md 12, scripts/determinism_valu_victim.py, scripts/determinism_probe3.py)
-        two = (P_out > 0 and P_in > 0 and R * S <= self._TWO_STREAM_SAMPLES
-               and (self.bf16 == 0 or os.environ.get('NU_BF16_TWO_STREAMS') == '1'))
+        two = P_out > 0 and P_in > 0 and R * S <= self._TWO_STREAM_SAMPLES and self.bf16 == 0
         ctx['two_streams'] = two
         out = {}
         fk = self.forked() if two else None

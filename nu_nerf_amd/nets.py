@@ -11,8 +11,6 @@ per-bounce bookkeeping of stage 2 can stay in torch while every GEMM runs in the
   StackFn     X[rows, K]            -> raw[rows, n_out]   one make_predictor stack          (field.py:371-408)
   MaterialsFn feat[P,256], x[P,3]   -> raw[P,6] (metallic, roughness, albedo(3), transmission; pre-sigmoid)
 """
-import os
-
 import torch
 
 from .engine import addr
@@ -507,7 +505,7 @@ class Stage1Nets:
         if X.shape[0] == 0:
             return X.new_zeros(0), X.new_zeros(0)
         la, lb = self.eng.small['ior_network'], self.eng.small['thickness_network']
-        if not _same_shape_pair(la, lb) or os.environ.get('NU_S2_IOR_PAIR') == '0':
+        if not _same_shape_pair(la, lb):
             return self.ior(X), self.thickness(X)
         return IorPairFn.apply(self.eng, la, lb, X, self.ior_names + self.thick_names, self.token())
 
@@ -525,6 +523,6 @@ class Stage1Nets:
             names_union = [n for nm in which for n in self.stack[nm][1]]
             _own_range(self.eng, names_union)                 # one contiguous range of the flat buffer (asserted)
             u = self._unions[key] = (tuple(self.stack[nm][0] for nm in which), layers_union, names_union)
-        if os.environ.get('NU_S2_STACKS') == '0' or any(X.shape[0] == 0 for X in Xs):      # development switch (A/B): one op per stack
+        if any(X.shape[0] == 0 for X in Xs):              # one op per stack
             return tuple(self.predictor(nm, X) for nm, X in zip(which, Xs))
         return StacksFn.apply(self.eng, u[0], u[1], u[2], self.token(), *Xs)

@@ -308,7 +308,7 @@ class Stage2Renderer(nn.Module):
             root = root.index_select(0, cont_idx)
         return segs, valid[:, None]
 
-    _TWO_STREAM_RAYS = int(os.environ.get('NU_S2_TWO_STREAM_RAYS', 1 << 20))      # 0: inner segment on the caller's stream
+    _TWO_STREAM_RAYS = 1 << 20      # 0: inner segment on the caller's stream
 
     def _inner_segment(self, n2, sg, cos_anneal_ratio, step, s):
         """The samples of the inner segment that lie inside the unit sphere (renderer_zerothick.py:1886-1915): inner SDF + normal,
@@ -383,7 +383,7 @@ class Stage2Renderer(nn.Module):
         # The inner segment (inner engine: SDF, NeuS alpha, inner shading) and the outer samples of all segments (stage-1 engine:
         # NeRF++) do not depend on each other, and the inner segment's GEMMs run on small point sets that leave most of the chip
         # idle: the inner segment is enqueued on the inner engine's side stream first and the NeRF++ pass on the current stream
-        # beside it (measured: -5 % at 1024 rays, -2..6 % at 4096; `NU_S2_TWO_STREAM_RAYS=0` switches it off); the
+        # beside it (measured: -5 % at 1024 rays, -2..6 % at 4096; `_TWO_STREAM_RAYS = 0` switches it off); the
         # autograd engine runs each node's backward on its forward stream, so the backward passes overlap the same way.  The two
         # engines have separate reduction arenas and descriptor tables; tensors that cross the fork / join are recorded on the
         # stream that reads them.

@@ -34,4 +34,4 @@ for P in (2048, 8192, 16384, 32768, 65536, 262144):
         eng._fused_sdf = on
         res[name] = time_it(lambda: eng.sdf_forward(addr(X), 3, P, keep=False, want_feat=False))
     print(f"P={P:7d}: layered {res['layered']:8.1f} us ({P * FL / res['layered'] / 1e6:6.1f} TFLOP/s)   fused {res['fused']:8.1f} us "
-          f"({P * FL / res['fused'] / 1e6:6.1f} TFLOP/s)   NU_FUSED_SDF_TM={os.environ.get('NU_FUSED_SDF_TM', 'rule')}")
+          f"({P * FL / res['fused'] / 1e6:6.1f} TFLOP/s)")

@@ -1,5 +1,5 @@
-"""Development aid: records visited per ray by the closest-hit kernels (needs a library built with -DNU_LBVH_STATS, where t_out
-carries the count; see scripts/README.md).  usage: NU_NERF_LIB=.../libnunerf_stats.so [NU_LBVH_QUAD=0] python3 scripts/lbvh_step_stats.py"""
+"""Development aid: records visited per ray by the closest-hit kernel (needs a library built with -DNU_LBVH_STATS, where t_out
+carries the count; see scripts/README.md).  usage: NU_NERF_LIB=.../libnunerf_stats.so python3 scripts/lbvh_step_stats.py"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -16,4 +16,4 @@ for name, maker in (("object-aimed", make_object_rays), ("camera", make_rays)):
     ray = torch.from_numpy(np.concatenate([r['rays_o'], r['rays_d'] / np.linalg.norm(r['rays_d'], axis=1, keepdims=True)], 1).astype(np.float32)).to(dev)
     hit, idx, t = bvh.intersect(ray, return_t=True)
     s = t.cpu().numpy()
-    print(f"{name:13s} NU_LBVH_QUAD={os.environ.get('NU_LBVH_QUAD', 'rule')}: records visited per ray: mean {s.mean():.1f}  median {np.median(s):.0f}  p90 {np.percentile(s, 90):.0f}  max {s.max():.0f}")
+    print(f"{name:13s} records visited per ray: mean {s.mean():.1f}  median {np.median(s):.0f}  p90 {np.percentile(s, 90):.0f}  max {s.max():.0f}")
