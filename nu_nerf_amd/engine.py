@@ -164,9 +164,6 @@ class Stage1Engine:
         self.ld_ol = 160 if self.sphere_direction else 96               # outer_light input 144 / 72 (field.py:594-597)
         self.ld_rl = rup(2 * self.refrac_dim, 32)
         lib = self.lib
-        for fn in ("nu_wgrad_workspace_bytes", "nu_skinny_bwd_workspace_bytes", "nu_colsum_workspace_bytes",
-                   "nu_gemm_tn_workspace_bytes", "nu_neus_alpha_bwd_workspace_bytes"):
-            getattr(lib, fn).restype = c_ll
         assert lib.nu_pack_desc_size() == ctypes.sizeof(PackDesc), "PackDesc ABI mismatch"
         assert lib.nu_reduce_desc_size() == ctypes.sizeof(ReduceDesc), "ReduceDesc ABI mismatch"
         assert lib.nu_gemm_nt_size() == ctypes.sizeof(GemmNT) and lib.nu_gemm_tn_size() == ctypes.sizeof(GemmTN), "GEMM ABI mismatch"
@@ -352,7 +349,7 @@ class Stage1Engine:
             self._ctx.arena, self._ctx.arena_floats = self._arena.data_ptr(), self._arena.numel()
 
     def flush_reductions(self):
-        L.check(self.lib.nu_ctx_flush(ctypes.byref(self._ctx), self.stream()), "nu_ctx_flush")
+        self.lib.nu_ctx_flush(ctypes.byref(self._ctx), self.stream())
 
     def _forced_flush(self):
         """A flush forced by a full arena / descriptor table in the MIDDLE of a pass.  While the engine is forked (two streams feed
@@ -363,7 +360,7 @@ class Stage1Engine:
                                        "NU_ARENA_FLOATS or lower Stage1Engine._TWO_STREAM_SAMPLES (NU_ERR_WORKSPACE)")
         # reductions only: the weight gradients still queued keep waiting for the end of their pass (their split must not
         # depend on when the arena happened to fill)
-        L.check(self.lib.nu_ctx_reduce(ctypes.byref(self._ctx), self.stream()), "nu_ctx_reduce")
+        self.lib.nu_ctx_reduce(ctypes.byref(self._ctx), self.stream())
 
     # ------------------------------------------------------------------ layer tables
     def _build_layers(self):
@@ -630,16 +627,14 @@ class Stage1Engine:
         """Fold weight-norm, pad/permute and transpose every layer's weight: one launch."""
         if self._desc_dev is None or self._ptr_sig != self._signature():
             self._upload_descs()
-        L.check(self.lib.nu_pack_layers(c_p(self._desc_dev.data_ptr()), len(self.layers), self.total_rows, self.stream()),
-                "nu_pack_layers")
+        self.lib.nu_pack_layers(self._desc_dev.data_ptr(), len(self.layers), self.total_rows, self.stream())
 
     def unpack_grads(self, flat, layers=None):
         """Weight-norm / plain weight gradients from the packed dW tables into `flat`.  layers: only these (consecutive entries of
         self.layers -- one network of a stage-2 op): every other slot of `flat` stays untouched."""
         self.flush_reductions()
         if layers is None:
-            L.check(self.lib.nu_unpack_grads(c_p(self._desc_dev.data_ptr()), len(self.layers), self.total_rows,
-                                             c_p(flat.data_ptr()), self.stream()), "nu_unpack_grads")
+            self.lib.nu_unpack_grads(self._desc_dev.data_ptr(), len(self.layers), self.total_rows, flat.data_ptr(), self.stream())
             return
         key = id(layers)
         rng = self.__dict__.setdefault('_unpack_ranges', {}).get(key)
@@ -650,8 +645,7 @@ class Stage1Engine:
                     raise ValueError("unpack_grads(layers=...): the layers are not consecutive in the descriptor table")
                 rows += l.N
             rng = self._unpack_ranges[key] = (layers, row0, rows)
-        L.check(self.lib.nu_unpack_grads_range(c_p(self._desc_dev.data_ptr()), len(self.layers), rng[1], rng[2], c_p(flat.data_ptr()),
-                                               self.stream()), "nu_unpack_grads_range")
+        self.lib.nu_unpack_grads_range(self._desc_dev.data_ptr(), len(self.layers), rng[1], rng[2], flat.data_ptr(), self.stream())
 
     # ------------------------------------------------------------------ raw launches
     def nt(self, A, lda, B, ldb, M, N, K, C, ldc, epi, *, C2=0, ldc2=0, bias=0, H=0, ldh=0, D=0, ldd=0, Cadd=0,
@@ -668,7 +662,7 @@ class Stage1Engine:
         if kt is not None:
             e0, e1 = self._event_pair()
             e0.record()
-        L.check(self.lib.nu_gemm_nt_ex(ctypes.byref(g), self.stream()), "nu_gemm_nt_ex")
+        self.lib.nu_gemm_nt_ex(ctypes.byref(g), self.stream())
         if kt is not None:
             e1.record()
             reads_h = bool(H) and not (mask is not None and epi in (EPI_MUL_DRELU, EPI_B_RELU))   # sign bits replace H
@@ -694,7 +688,7 @@ class Stage1Engine:
         if kt is not None:
             e0, e1 = self._event_pair()
             e0.record()
-        L.check(self.lib.nu_gemm_nt_batch(arr, len(descs), self.stream()), "nu_gemm_nt_batch")
+        self.lib.nu_gemm_nt_batch(arr, len(descs), self.stream())
         if kt is not None:
             e1.record()
             fl = by = 0.0
@@ -785,14 +779,13 @@ class Stage1Engine:
         self._ensure_arena()
         g = GemmTN(A0, lda0, B0, ldb0, A1, lda1, B1, ldb1, P, N1, N2, 0, 0, 1, groups, sA0, sB0, sA1, sB1, 0, 0, self.bf16, 0)
         npair = 2 if A1 else 1
-        L.check(self.lib.nu_wgrad_defer(ctypes.byref(self._ctx), ctypes.byref(g), c_p(dW), ldw, c_ll(sW), c_p(db), c_ll(sDb),
-                                        ctypes.c_double(2.0 * P * N1 * N2 * groups * npair),
-                                        ctypes.c_double(4.0 * groups * (npair * P * (N1 + N2) + N1 * N2)), self.stream()), "nu_wgrad_defer")
+        self.lib.nu_wgrad_defer(ctypes.byref(self._ctx), ctypes.byref(g), dW, ldw, sW, db, sDb, 2.0 * P * N1 * N2 * groups * npair,
+                                4.0 * groups * (npair * P * (N1 + N2) + N1 * N2), self.stream())
         if self._wg_depth == 0:
             self.flush_wgrads()
 
     def flush_wgrads(self):
-        L.check(self.lib.nu_wgrad_flush(ctypes.byref(self._ctx), self.stream()), "nu_wgrad_flush")
+        self.lib.nu_wgrad_flush(ctypes.byref(self._ctx), self.stream())
 
     def wgrad_batch(self):
         """Context of a backward pass sequenced from Python: weight gradients queued inside are launched together at the exit
@@ -821,23 +814,20 @@ class Stage1Engine:
         return _Batch()
 
     def skinny_fwd(self, H, ldh, P, K, Ws, ldw, b, NO, out, ldo):
-        L.check(self.lib.nu_skinny_fwd(c_p(H), ldh, P, K, c_p(Ws), ldw, c_p(b), NO, c_p(out), ldo, self.stream()),
-                "nu_skinny_fwd")
+        self.lib.nu_skinny_fwd(H, ldh, P, K, Ws, ldw, b, NO, out, ldo, self.stream())
 
     def skinny_bwd(self, dy, ldy, H, ldh, P, K, Ws, ldw, NO, dH, lddh, relu_mask, accumulate, dWs, lddw, db):
         if self._ctx.ndesc + 2 > self._rd_cap:
             self._forced_flush()
         ws, nb = self._arena_take(self.lib.nu_skinny_bwd_workspace_bytes(K, NO))
-        L.check(self.lib.nu_skinny_bwd_enqueue(c_p(dy), ldy, c_p(H), ldh, P, K, c_p(Ws), ldw, NO, c_p(dH), lddh, relu_mask,
-                                               accumulate, c_p(dWs), lddw, c_p(db), c_p(ws), c_ll(nb), self._rd,
-                                               self._ndesc_p, self._rd_cap, self.stream()), "nu_skinny_bwd_enqueue")
+        self.lib.nu_skinny_bwd_enqueue(dy, ldy, H, ldh, P, K, Ws, ldw, NO, dH, lddh, relu_mask, accumulate, dWs,
+                                       lddw, db, ws, nb, self._rd, self._ndesc_p, self._rd_cap, self.stream())
 
     def colsum(self, A, lda, P, ncols, out, accumulate):
         if self._ctx.ndesc + 1 > self._rd_cap:
             self._forced_flush()
         ws, nb = self._arena_take(self.lib.nu_colsum_workspace_bytes(ncols))
-        L.check(self.lib.nu_colsum_enqueue(c_p(A), lda, P, ncols, c_p(out), accumulate, c_p(ws), c_ll(nb), self._rd,
-                                           self._ndesc_p, self._rd_cap, self.stream()), "nu_colsum_enqueue")
+        self.lib.nu_colsum_enqueue(A, lda, P, ncols, out, accumulate, ws, nb, self._rd, self._ndesc_p, self._rd_cap, self.stream())
 
     # ------------------------------------------------------------------ SDF network
     def sdf_forward(self, X, x_ld, P, *, keep=True, want_feat=True):
@@ -852,13 +842,13 @@ class Stage1Engine:
             # Measured (scripts/bench_fused_sdf.py, profiles/r03): 93 vs 122 us at 8 192 points, 153 vs 186 at 16 384, 304 vs 315
             # at 32 768; from 65 536 points on the layered GEMMs (two workgroups per CU) are 4 % faster, so those keep them
             sdf = e(P)
-            L.check(lib.nu_sdf_fused_fwd(ctypes.byref(self._sdf_net), c_p(X), x_ld, P, c_p(addr(sdf)), S), "nu_sdf_fused_fwd")
+            lib.nu_sdf_fused_fwd(ctypes.byref(self._sdf_net), X, x_ld, P, addr(sdf), S)
             return {'P': P, 'sdf': sdf}
         if not keep and not want_feat and self.h16 and self._fused_sdf and getattr(self, '_sdf_net', None) is not None:
             # bf16 storage: the same network in ONE kernel (csrc/fused_sdf.hip, sdf_fused16_fwd_kernel), bit-identical to the layered
             # bf16-storage path below -- a point costs 12 bytes in and 4 out instead of 1 KB per layer
             sdf = e(P)
-            L.check(lib.nu_sdf_fused16_fwd(ctypes.byref(self._sdf_net), c_p(X), x_ld, P, c_p(addr(sdf)), S), "nu_sdf_fused16_fwd")
+            lib.nu_sdf_fused16_fwd(ctypes.byref(self._sdf_net), X, x_ld, P, addr(sdf), S)
             return {'P': P, 'sdf': sdf}
         a = {'P': P}
         a['E'] = e(P, 64)
@@ -880,11 +870,9 @@ class Stage1Engine:
             a['sdf'] = None if want_feat else e(P)
             cb.sdf = addr(a['sdf'])
             a['cb'] = cb
-            L.check(lib.nu_sdf_mlp_fwd(ctypes.byref(self._ctx), ctypes.byref(self._sdf_net), c_p(X), x_ld, ctypes.byref(cb),
-                                       1 if want_feat else 0, S), "nu_sdf_mlp_fwd")
+            lib.nu_sdf_mlp_fwd(ctypes.byref(self._ctx), ctypes.byref(self._sdf_net), X, x_ld, ctypes.byref(cb), 1 if want_feat else 0, S)
             return a
-        L.check(lib.nu_sdf_embed(c_p(X), x_ld, P, c_p(addr(a['E'])), c_p(addr(a['U4'])),
-                                 c_p(addr(a['YX'])), S), "nu_sdf_embed")
+        lib.nu_sdf_embed(X, x_ld, P, addr(a['E']), addr(a['U4']), addr(a['YX']), S)
         src, lds, K = a['E'], 64, 64
         for l in range(8):
             N = ls[l].N
@@ -914,10 +902,9 @@ class Stage1Engine:
             for l in range(8):
                 cb.D[l] = addr(D[l])
             cb.G0, cb.n = addr(a['G0']), addr(a['n'])
-            L.check(lib.nu_sdf_mlp_normal(ctypes.byref(self._ctx), ctypes.byref(self._sdf_net), ctypes.byref(cb), S), "nu_sdf_mlp_normal")
+            lib.nu_sdf_mlp_normal(ctypes.byref(self._ctx), ctypes.byref(self._sdf_net), ctypes.byref(cb), S)
             return a['n']
-        L.check(lib.nu_rowscale_dsp(c_p(addr(H[8])), 256, P, 256, c_p(addr(*ls[8].Wp)), c_p(addr(D[7])), 256, S),
-                "nu_rowscale_dsp")
+        lib.nu_rowscale_dsp(addr(H[8]), 256, P, 256, addr(*ls[8].Wp), addr(D[7]), 256, S)
         for l in range(7, 0, -1):
             # G_{u_l} = D_l . Wp_l ; delta_{l-1} = G[:, :N_{l-1}] * sp'(H_l)
             Kred = rup(ls[l].N, 32)                    # reduction over layer l's outputs (217 -> 224 at l = 3)
@@ -933,8 +920,7 @@ class Stage1Engine:
         self.nt(addr(D[0]), 256, addr(*ls[0].WpT), ls[0].ldT, P, 39, 256, addr(G0), 64, EPI_PLAIN, zero_to=64)
         a['G0'] = G0
         a['n'] = e(P, 3)
-        L.check(lib.nu_embed_jt(c_p(addr(a['E'])), c_p(addr(G0)), 64, c_p(addr(D[3], 217)), 256, P, c_p(addr(a['n'])), S),
-                "nu_embed_jt")
+        lib.nu_embed_jt(addr(a['E']), addr(G0), 64, addr(D[3], 217), 256, P, addr(a['n']), S)
         return a['n']
 
     def sdf_backward(self, a, dYX, nbar, flat, dx=None):
@@ -968,8 +954,7 @@ class Stage1Engine:
                 cb.dE0 = addr(t)
             self._ensure_arena()
             self._ctx.flat = addr(flat)
-            L.check(lib.nu_sdf_mlp_bwd(ctypes.byref(self._ctx), ctypes.byref(self._sdf_net), ctypes.byref(cb), c_p(addr(dYX)),
-                                       c_p(addr(nbar)), c_p(addr(dx)), S), "nu_sdf_mlp_bwd")
+            lib.nu_sdf_mlp_bwd(ctypes.byref(self._ctx), ctypes.byref(self._sdf_net), ctypes.byref(cb), addr(dYX), addr(nbar), addr(dx), S)
             a['_bwd_keep'] = keep          # buffers stay referenced until the caller drops the activation dict
             return
         Cb = [None] * 8
@@ -978,7 +963,7 @@ class Stage1Engine:
             D = a['D']
             Q[0] = e(P, 64)
             Q[4] = e(P, 256)
-            L.check(lib.nu_embed_j(c_p(addr(E)), c_p(addr(nbar)), P, c_p(addr(Q[0])), c_p(addr(Q[4])), S), "nu_embed_j")
+            lib.nu_embed_j(addr(E), addr(nbar), P, addr(Q[0]), addr(Q[4]), S)
             src, lds, K = Q[0], 64, 64
             for l in range(8):
                 N = ls[l].N
@@ -1022,9 +1007,8 @@ class Stage1Engine:
         if dx is not None:
             dE0 = e(P, 64)
             self.nt(addr(A[0]), 256, addr(*ls[0].WpT), ls[0].ldT, P, 39, 256, addr(dE0), 64, EPI_PLAIN, zero_to=64)
-            L.check(lib.nu_embed_jt2(c_p(addr(E)), c_p(addr(dE0)), 64, c_p(addr(A[3], 217)), 256,
-                                     c_p(addr(a['G0']) if second else 0), 64, c_p(addr(a['D'][3], 217) if second else 0), 256,
-                                     c_p(addr(nbar) if second else 0), P, c_p(addr(dx)), 0, S), "nu_embed_jt2")
+            lib.nu_embed_jt2(addr(E), addr(dE0), 64, addr(A[3], 217), 256, addr(a['G0']) if second else 0, 64,
+                             addr(a['D'][3], 217) if second else 0, 256, addr(nbar) if second else 0, P, addr(dx), 0, S)
 
     def _sdf_cb(self, a):
         """The C buffer table of an activation dict (built on demand for dicts made by the Python-sequenced forward)."""
@@ -1099,12 +1083,11 @@ class Stage1Engine:
         rows_ol = 3 * P + R
         ld_ol, ld_rl, sph = self.ld_ol, self.ld_rl, 1 if self.sphere_direction else 0
         OLin, ILin, IWin, RLin, SD = e(rows_ol, ld_ol), e(2 * P, 128), e(P, 96), e(P, ld_rl), e(P, 8)
-        L.check(lib.nu_shade_encode_fwd(c_p(addr(a['n'])), c_p(addr(pt)), 8, c_p(addr(a['E'])), c_p(addr(Mraw)), 8, P, sph,
-                                        ld_ol, self.refrac_dim, ld_rl, c_p(addr(OLin)), c_p(addr(ILin)), c_p(addr(IWin)),
-                                        c_p(addr(RLin)), c_p(addr(SD)), S), "nu_shade_encode_fwd")
+        lib.nu_shade_encode_fwd(addr(a['n']), addr(pt), 8, addr(a['E']), addr(Mraw), 8, P, sph, ld_ol,
+                                self.refrac_dim, ld_rl, addr(OLin), addr(ILin), addr(IWin), addr(RLin), addr(SD), S)
         if R:
-            L.check(lib.nu_spec_encode(c_p(addr(extra_dirs)), c_p(addr(extra_pts)), R, sph if extra_pts is not None else 0,
-                                       c_p(addr(OLin, 3 * P * ld_ol)), ld_ol, S), "nu_spec_encode")
+            lib.nu_spec_encode(addr(extra_dirs), addr(extra_pts), R,
+                               sph if extra_pts is not None else 0, addr(OLin, 3 * P * ld_ol), ld_ol, S)
         s.update(OLin=OLin, ILin=ILin, IWin=IWin, RLin=RLin, SD=SD, R=R, rows_ol=rows_ol)
         # light predictors
         s['OLh'] = self.relu_stack_fwd(self.outer_light, OLin, ld_ol, rows_ol)
@@ -1119,10 +1102,8 @@ class Stage1Engine:
             self.skinny_fwd(addr(Hs[2]), 256, rows, 256, addr(*lay.Wp), 256, addr(lay.b), no, addr(out), ldo)
         s.update(OLo=OLo, ILo=ILo, IWo=IWo, RLo=RLo)
         s['aux'] = e(P, 4)
-        L.check(lib.nu_shade_combine_fwd(c_p(addr(Mraw)), 8, c_p(addr(OLo)), c_p(addr(ILo)), c_p(addr(IWo)),
-                                         c_p(addr(RLo)), c_p(addr(SD)), c_p(addr(self.lut)), c_p(addr(idx)), P,
-                                         c_f(self.exp_max), c_p(addr(color_rm)), c_p(addr(s['aux'])), S),
-                "nu_shade_combine_fwd")
+        lib.nu_shade_combine_fwd(addr(Mraw), 8, addr(OLo), addr(ILo), addr(IWo), addr(RLo), addr(SD),
+                                 addr(self.lut), addr(idx), P, self.exp_max, addr(color_rm), addr(s['aux']), S)
         return s
 
     def _c_shading_forward(self, a, pt, idx, P, color_rm, extra_dirs, extra_pts):
@@ -1148,9 +1129,8 @@ class Stage1Engine:
                 arr[j], marr[j] = addr(Hs[j]), addr(self.relu_mask(Hs[j], rows, 256))
             s[key] = Hs
         s['cb'] = cb
-        L.check(lib.nu_shading_stack_fwd(ctypes.byref(self._ctx), ctypes.byref(self._shade_net), ctypes.byref(cb), c_p(addr(a['YX'])),
-                                         c_p(addr(a['E'])), c_p(addr(a['n'])), c_p(addr(pt)), c_p(addr(idx)), c_p(addr(color_rm)), S),
-                "nu_shading_stack_fwd")
+        lib.nu_shading_stack_fwd(ctypes.byref(self._ctx), ctypes.byref(self._shade_net), ctypes.byref(cb),
+                                 addr(a['YX']), addr(a['E']), addr(a['n']), addr(pt), addr(idx), addr(color_rm), S)
         return s
 
     def _c_shading_backward(self, a, s, pt, idx, dcolor_rm, flat, d_spec_raw, d_occ_raw, d_mat_raw=None):
@@ -1159,9 +1139,9 @@ class Stage1Engine:
         cb = s['cb']
         dMraw, dOLo, dILo, dIWo, dRLo, dNoV = e(P, 8), e(rows_ol, 4), e(2 * P, 4), e(P), e(P, 4), e(P)
         cb.dMraw, cb.dOLo, cb.dILo, cb.dIWo, cb.dRLo, cb.dNoV = (addr(t) for t in (dMraw, dOLo, dILo, dIWo, dRLo, dNoV))
-        args = (ctypes.byref(self._ctx), ctypes.byref(self._shade_net), ctypes.byref(cb), c_p(addr(a['YX'])), c_p(addr(a['n'])),
-                c_p(addr(pt)), c_p(addr(idx)), c_p(addr(dcolor_rm)))
-        L.check(lib.nu_shading_stack_bwd(*args, 0, S), "nu_shading_stack_bwd(0)")
+        args = (ctypes.byref(self._ctx), ctypes.byref(self._shade_net), ctypes.byref(cb), addr(a['YX']), addr(a['n']), addr(pt),
+                addr(idx), addr(dcolor_rm))
+        lib.nu_shading_stack_bwd(*args, 0, S)
         if R:
             if d_spec_raw is not None:
                 dOLo[3 * P:, :3] = d_spec_raw
@@ -1189,7 +1169,7 @@ class Stage1Engine:
             cb.dM[j] = addr(dM[j])
         self._ensure_arena()
         self._ctx.flat = addr(flat)
-        L.check(lib.nu_shading_stack_bwd(*args, 1, S), "nu_shading_stack_bwd(1)")
+        lib.nu_shading_stack_bwd(*args, 1, S)
         return dYX, dn
 
     def shading_backward(self, a, s, pt, idx, dcolor_rm, flat, d_spec_raw=None, d_occ_raw=None, d_mat_raw=None):
@@ -1200,11 +1180,9 @@ class Stage1Engine:
         if self._use_c() and 'cb' in s:
             return self._c_shading_backward(a, s, pt, idx, dcolor_rm, flat, d_spec_raw, d_occ_raw, d_mat_raw)
         dMraw, dOLo, dILo, dIWo, dRLo, dNoV = e(P, 8), e(rows_ol, 4), e(2 * P, 4), e(P), e(P, 4), e(P)
-        L.check(lib.nu_shade_combine_bwd(c_p(addr(s['Mraw'])), 8, c_p(addr(s['OLo'])), c_p(addr(s['ILo'])),
-                                         c_p(addr(s['IWo'])), c_p(addr(s['RLo'])), c_p(addr(s['SD'])),
-                                         c_p(addr(self.lut)), c_p(addr(idx)), P, c_f(self.exp_max),
-                                         c_p(addr(dcolor_rm)), c_p(addr(dMraw)), c_p(addr(dOLo)), c_p(addr(dILo)),
-                                         c_p(addr(dIWo)), c_p(addr(dRLo)), c_p(addr(dNoV)), S), "nu_shade_combine_bwd")
+        lib.nu_shade_combine_bwd(addr(s['Mraw']), 8, addr(s['OLo']), addr(s['ILo']), addr(s['IWo']), addr(s['RLo']),
+                                 addr(s['SD']), addr(self.lut), addr(idx), P, self.exp_max, addr(dcolor_rm),
+                                 addr(dMraw), addr(dOLo), addr(dILo), addr(dIWo), addr(dRLo), addr(dNoV), S)
         if R:
             if d_spec_raw is not None:
                 dOLo[3 * P:, :3] = d_spec_raw
@@ -1230,9 +1208,8 @@ class Stage1Engine:
                                 addr(*head.dWp), head.ldd, addr(flat, head.db_off))
                 self.relu_stack_bwd(layers, X, ldx, rows, Hs, dH3, flat, dX, lddx, dxc)
             dn = e(P, 3)
-            L.check(lib.nu_shade_encode_bwd(c_p(addr(a['n'])), c_p(addr(pt)), 8, c_p(addr(s['SD'])), c_p(addr(dOLin)), ld_ol,
-                                            1 if self.sphere_direction else 0, c_p(addr(dILin)), c_p(addr(dNoV)), P,
-                                            c_p(addr(dn)), c_p(addr(dMraw)), 8, S), "nu_shade_encode_bwd")
+            lib.nu_shade_encode_bwd(addr(a['n']), addr(pt), 8, addr(s['SD']), addr(dOLin), ld_ol,
+                                    1 if self.sphere_direction else 0, addr(dILin), addr(dNoV), P, addr(dn), addr(dMraw), 8, S)
             # materials backward
             db0, db12, db6 = self.mat_db
             dM3 = wb.keep(e(P, 1024))
@@ -1269,14 +1246,12 @@ class Stage1Engine:
                     cb.mask[i] = addr(self.relu_mask(H[i], P, 256))
             HV, sig, rgb = e(P, 128), e(P), e(P, 4)
             cb.V, cb.HV, cb.sig, cb.rgb = addr(V), addr(HV), addr(sig), addr(rgb)
-            L.check(lib.nu_nerfpp_mlp_fwd(ctypes.byref(self._ctx), ctypes.byref(self._nerf_net), c_p(addr(pt)), pt.shape[1],
-                                          ctypes.byref(cb), S), "nu_nerfpp_mlp_fwd")
+            lib.nu_nerfpp_mlp_fwd(ctypes.byref(self._ctx), ctypes.byref(self._nerf_net), addr(pt), pt.shape[1], ctypes.byref(cb), S)
             if alpha_rm is not None:
-                L.check(lib.nu_nerf_act_fwd(c_p(addr(sig)), 1, c_p(addr(rgb)), 4, c_p(addr(pt)), c_p(addr(idx)), P,
-                                            c_p(addr(alpha_rm)), c_p(addr(color_rm)), S), "nu_nerf_act_fwd")
+                lib.nu_nerf_act_fwd(addr(sig), 1, addr(rgb), 4, addr(pt), addr(idx), P, addr(alpha_rm), addr(color_rm), S)
             b.update(H=H, V=V, HV=HV, sig=sig, rgb=rgb, cb=cb)
             return b
-        L.check(lib.nu_nerf_embed(c_p(addr(pt)), pt.shape[1], P, c_p(addr(E4)), c_p(addr(U5)), c_p(addr(V)), S), "nu_nerf_embed")
+        lib.nu_nerf_embed(addr(pt), pt.shape[1], P, addr(E4), addr(U5), addr(V), S)
         H = [E4]
         src, lds = E4, 96
         for i in range(8):
@@ -1298,8 +1273,7 @@ class Stage1Engine:
         rgb = e(P, 4)
         self.skinny_fwd(addr(HV), 128, P, 128, addr(*self.nerf_rgb.Wp), 128, addr(self.nerf_rgb.b), 3, addr(rgb), 4)
         if alpha_rm is not None:
-            L.check(lib.nu_nerf_act_fwd(c_p(addr(sig)), 1, c_p(addr(rgb)), 4, c_p(addr(pt)), c_p(addr(idx)), P,
-                                        c_p(addr(alpha_rm)), c_p(addr(color_rm)), S), "nu_nerf_act_fwd")
+            lib.nu_nerf_act_fwd(addr(sig), 1, addr(rgb), 4, addr(pt), addr(idx), P, addr(alpha_rm), addr(color_rm), S)
         b.update(V=V, HV=HV, sig=sig, rgb=rgb)
         return b
 
@@ -1312,9 +1286,8 @@ class Stage1Engine:
         want_in = dx is not None
         if dsig is None:
             dsig, drgb = e(P), e(P, 4)
-            L.check(lib.nu_nerf_act_bwd(c_p(addr(b['sig'])), 1, c_p(addr(b['rgb'])), 4, c_p(addr(pt)), c_p(addr(idx)), P,
-                                        c_p(addr(dalpha_rm)), c_p(addr(dcolor_rm)), c_p(addr(dsig)), 1, c_p(addr(drgb)), 4, S),
-                    "nu_nerf_act_bwd")
+            lib.nu_nerf_act_bwd(addr(b['sig']), 1, addr(b['rgb']), 4, addr(pt), addr(idx), P,
+                                addr(dalpha_rm), addr(dcolor_rm), addr(dsig), 1, addr(drgb), 4, S)
         if self._use_c():
             cb = b.get('cb')
             if cb is None:                 # forward was sequenced from Python
@@ -1338,8 +1311,8 @@ class Stage1Engine:
                 cb.dE4 = cb.dx = cb.ddir = 0
             self._ensure_arena()
             self._ctx.flat = addr(flat)
-            L.check(lib.nu_nerfpp_mlp_bwd(ctypes.byref(self._ctx), ctypes.byref(self._nerf_net), c_p(addr(pt)), pt.shape[1],
-                                          ctypes.byref(cb), c_p(addr(dsig)), c_p(addr(drgb)), S), "nu_nerfpp_mlp_bwd")
+            lib.nu_nerfpp_mlp_bwd(ctypes.byref(self._ctx), ctypes.byref(self._nerf_net), addr(pt),
+                                  pt.shape[1], ctypes.byref(cb), addr(dsig), addr(drgb), S)
             return
         with self.wgrad_batch() as wb:        # the pass's weight gradients: one queue, launched together at the end of the block
             # rgb head -> view layer
@@ -1382,9 +1355,8 @@ class Stage1Engine:
                 elif want_in:
                     dE4 = wb.keep(e(P, 96))
                     self.nt(addr(dA), lda, addr(*lay.WpT), lay.ldT, P, 84, 256, addr(dE4), 96, EPI_PLAIN, zero_to=96)
-                    L.check(lib.nu_nerf_embed_bwd(c_p(addr(pt)), pt.shape[1], c_p(addr(H[0])), c_p(addr(b['V'])), c_p(addr(dE4)), 96,
-                                                  c_p(addr(dskip, 256)), 352, c_p(addr(dF, 256)), ldf, P, c_p(addr(dx)),
-                                                  c_p(addr(ddir)), S), "nu_nerf_embed_bwd")
+                    lib.nu_nerf_embed_bwd(addr(pt), pt.shape[1], addr(H[0]), addr(b['V']), addr(dE4), 96,
+                                          addr(dskip, 256), 352, addr(dF, 256), ldf, P, addr(dx), addr(ddir), S)
 
     # ------------------------------------------------------------------ sampler (no grad)
     def _sampler_consts(self, Nc, Nbg, n_new):
@@ -1415,26 +1387,22 @@ class Stage1Engine:
             u1, u2 = u1.contiguous(), u2.contiguous()
         e = self.empty
         z, zbg, X = e(R, Nc), e(R, Nbg), e(R * Nc, 3)
-        L.check(lib.nu_sample_coarse(c_p(addr(o)), c_p(addr(d)), c_p(addr(near)), c_p(addr(far)), c_p(addr(lin)),
-                                     c_p(addr(lower if perturb > 0 else zo_lin)), c_p(addr(upper)),
-                                     c_p(addr(u1) if perturb > 0 else 0), c_p(addr(u2) if perturb > 0 else 0), R, Nc, Nbg,
-                                     c_p(addr(z)), c_p(addr(zbg)), c_p(addr(X)), S), "nu_sample_coarse")
+        lib.nu_sample_coarse(addr(o), addr(d), addr(near), addr(far), addr(lin), addr(lower if perturb > 0 else zo_lin), addr(upper),
+                             addr(u1) if perturb > 0 else 0, addr(u2) if perturb > 0 else 0, R, Nc, Nbg, addr(z), addr(zbg), addr(X), S)
         sdf = self.sdf_forward(addr(X), 3, R * Nc, keep=False, want_feat=False)['sdf']
         sn = Nc
         var = self.p['deviation_network.variance']
         for i in range(steps):
             zn, Xn = e(R, n_new), e(R * n_new, 3)
-            L.check(lib.nu_upsample(c_p(addr(o)), c_p(addr(d)), c_p(addr(z)), c_p(addr(sdf)), R, sn, c_p(addr(var)),
-                                    c_f(64.0 * 2 ** i), 1 if cfg['clip_sample_variance'] else 0, c_p(addr(uv)), n_new,
-                                    c_p(addr(zn)), c_p(addr(Xn)), S), "nu_upsample")
+            lib.nu_upsample(addr(o), addr(d), addr(z), addr(sdf), R, sn, addr(var), 64.0 * 2 ** i,
+                            1 if cfg['clip_sample_variance'] else 0, addr(uv), n_new, addr(zn), addr(Xn), S)
             last = i + 1 == steps
             sdf_n = None if last else self.sdf_forward(addr(Xn), 3, R * n_new, keep=False, want_feat=False)['sdf']
             zo, so = e(R, sn + n_new), (None if last else e(R, sn + n_new))
-            L.check(lib.nu_merge_sorted(c_p(addr(z)), c_p(addr(sdf)), sn, c_p(addr(zn)), c_p(addr(sdf_n)), n_new, R,
-                                        c_p(addr(zo)), c_p(addr(so)), S), "nu_merge_sorted")
+            lib.nu_merge_sorted(addr(z), addr(sdf), sn, addr(zn), addr(sdf_n), n_new, R, addr(zo), addr(so), S)
             z, sdf, sn = zo, so, sn + n_new
         out = e(R, sn + Nbg)
-        L.check(lib.nu_concat_cols(c_p(addr(z)), sn, c_p(addr(zbg)), Nbg, R, c_p(addr(out)), S), "nu_concat_cols")
+        lib.nu_concat_cols(addr(z), sn, addr(zbg), Nbg, R, addr(out), S)
         return out
 
     # ------------------------------------------------------------------ render_core
@@ -1455,9 +1423,8 @@ class Stage1Engine:
                 ctx['occ_idx'] = torch.nonzero(m_)[:, 0]
             gerr = e(P_in)
             var = self.p['deviation_network.variance']
-            L.check(lib.nu_neus_alpha_fwd(c_p(addr(a['YX'])), 288, c_p(addr(a['n'])), c_p(addr(pt_in)), c_p(addr(idx_in)),
-                                          P_in, c_p(addr(var)), c_f(anneal), c_p(addr(alpha_rm)), c_p(addr(gerr)),
-                                          c_p(addr(color_rm)), S_), "nu_neus_alpha_fwd")
+            lib.nu_neus_alpha_fwd(addr(a['YX']), 288, addr(a['n']), addr(pt_in), addr(idx_in), P_in,
+                                  addr(var), anneal, addr(alpha_rm), addr(gerr), addr(color_rm), S_)
             s = self.shading_forward(a, pt_in, idx_in, P_in, color_rm, extra_dirs=du, extra_pts=spec_pts)
             ctx.update(sdf=a, shade=s)
             out['gradient_error'] = gerr
@@ -1475,16 +1442,14 @@ class Stage1Engine:
         R, S = z.shape
         o, d, z = o.contiguous(), d.contiguous(), z.contiguous()
         cnt, off, tot = e(R, dtype=torch.int32), e(R, dtype=torch.int32), e(2, dtype=torch.int32)
-        L.check(lib.nu_partition_count(c_p(addr(o)), c_p(addr(d)), c_p(addr(z)), R, S, c_p(addr(cnt)), c_p(addr(off)),
-                                       c_p(addr(tot)), S_), "nu_partition_count")
+        lib.nu_partition_count(addr(o), addr(d), addr(z), R, S, addr(cnt), addr(off), addr(tot), S_)
         P_in = int(tot[0].item())
         P_out = R * S - P_in
         pt_in, idx_in = e(max(P_in, 1), 8), e(max(P_in, 1), dtype=torch.int32)
         pt_out, idx_out = e(max(P_out, 1), 8), e(max(P_out, 1), dtype=torch.int32)
         inner_rm = e(R * S, dtype=torch.uint8)
-        L.check(lib.nu_partition_write(c_p(addr(o)), c_p(addr(d)), c_p(addr(z)), R, S, c_p(addr(off)), c_p(addr(pt_in)),
-                                       c_p(addr(idx_in)), c_p(addr(pt_out)), c_p(addr(idx_out)), c_p(addr(inner_rm)), S_),
-                "nu_partition_write")
+        lib.nu_partition_write(addr(o), addr(d), addr(z), R, S, addr(off), addr(pt_in),
+                               addr(idx_in), addr(pt_out), addr(idx_out), addr(inner_rm), S_)
         alpha_rm, color_rm = e(R * S), e(R * S, 4)
         ctx = dict(R=R, S=S, P_in=P_in, P_out=P_out, P_in_dev=tot[:1], pt_in=pt_in, idx_in=idx_in, pt_out=pt_out, idx_out=idx_out,
                    inner_rm=inner_rm, alpha_rm=alpha_rm, color_rm=color_rm, anneal=float(anneal))
@@ -1508,9 +1473,8 @@ class Stage1Engine:
                 fk.__exit__(None, None, None)
         weights = e(R, S) if want_weights else None
         rgb, acc, rgb_bg, nrm_sum = e(R, 3), e(R), e(R, 3), e(R)
-        L.check(lib.nu_composite_fwd(c_p(addr(alpha_rm)), c_p(addr(color_rm)), c_p(addr(inner_rm)), R, S,
-                                     c_p(addr(weights)), c_p(addr(rgb)), c_p(addr(acc)), c_p(addr(rgb_bg)),
-                                     c_p(addr(nrm_sum)), S_), "nu_composite_fwd")
+        lib.nu_composite_fwd(addr(alpha_rm), addr(color_rm), addr(inner_rm), R, S, addr(weights),
+                             addr(rgb), addr(acc), addr(rgb_bg), addr(nrm_sum), S_)
         out.update(rgb=rgb, acc=acc, rgb_bg=rgb_bg, weights=weights, nrm_sum=nrm_sum)
         self.last_ctx = ctx
         return out, ctx
@@ -1528,9 +1492,8 @@ class Stage1Engine:
         # list dies as soon as addr() returns and its block may be handed to the next allocation)
         d_rgb, d_acc, d_rgb_bg, d_nrm_sum, d_gerr = (None if t is None else t.contiguous()
                                                      for t in (d_rgb, d_acc, d_rgb_bg, d_nrm_sum, d_gerr))
-        L.check(lib.nu_composite_bwd(c_p(addr(ctx['alpha_rm'])), c_p(addr(ctx['color_rm'])), c_p(addr(ctx['inner_rm'])),
-                                     R, S, c_p(addr(d_rgb)), c_p(addr(d_acc)), c_p(addr(d_rgb_bg)), c_p(addr(d_nrm_sum)),
-                                     c_p(addr(dalpha_rm)), c_p(addr(dcolor_rm)), S_), "nu_composite_bwd")
+        lib.nu_composite_bwd(addr(ctx['alpha_rm']), addr(ctx['color_rm']), addr(ctx['inner_rm']), R, S, addr(d_rgb),
+                             addr(d_acc), addr(d_rgb_bg), addr(d_nrm_sum), addr(dalpha_rm), addr(dcolor_rm), S_)
         two = ctx.get('two_streams', False)
         fk = self.forked() if two else None
         side = fk.__enter__() if two else None
@@ -1580,13 +1543,10 @@ class Stage1Engine:
                 if self._ctx.ndesc + 1 > self._rd_cap:
                     self._forced_flush()
                 ws, nb = self._arena_take(lib.nu_neus_alpha_bwd_workspace_bytes(P_in))
-            L.check(lib.nu_neus_alpha_bwd(c_p(addr(a['YX'])), 288, c_p(addr(a['n'])), c_p(addr(ctx['pt_in'])),
-                                          c_p(addr(ctx['idx_in'])), P_in, c_p(addr(var)), c_f(ctx['anneal']),
-                                          c_p(addr(dalpha_rm)), c_p(addr(d_gerr)),
-                                          c_p(addr(dn)), c_p(addr(dcolor_rm) if d_nrm_sum is not None else 0), c_p(addr(dYX)), 288,
-                                          c_p(addr(nbar)),
-                                          c_p(addr(flat, self.var_off) if train_inv_s else 0), c_p(ws), c_ll(nb), self._rd, self._ndesc_p,
-                                          self._rd_cap, S_), "nu_neus_alpha_bwd")
+            lib.nu_neus_alpha_bwd(addr(a['YX']), 288, addr(a['n']), addr(ctx['pt_in']), addr(ctx['idx_in']), P_in, addr(var),
+                                  ctx['anneal'], addr(dalpha_rm), addr(d_gerr), addr(dn),
+                                  addr(dcolor_rm) if d_nrm_sum is not None else 0, addr(dYX), 288, addr(nbar),
+                                  addr(flat, self.var_off) if train_inv_s else 0, ws, nb, self._rd, self._ndesc_p, self._rd_cap, S_)
             if d_sdf_in is not None:
                 dYX[:, 0] += d_sdf_in
             self.sdf_backward(a, dYX, nbar, flat)
@@ -1610,18 +1570,15 @@ class Stage1Engine:
         lin, uv = self._pc
         zero = self.zeros(M)
         z, X = e(M, sn0), e(M * sn0, 3)
-        L.check(lib.nu_sample_coarse(c_p(addr(pts)), c_p(addr(dirs)), c_p(addr(zero)), c_p(addr(max_dist)), c_p(addr(lin)),
-                                     c_p(0), c_p(0), c_p(0), c_p(0), M, sn0, 0, c_p(addr(z)), c_p(0), c_p(addr(X)), S),
-                "nu_sample_coarse")
+        lib.nu_sample_coarse(addr(pts), addr(dirs), addr(zero), addr(max_dist), addr(lin),
+                             None, None, None, None, M, sn0, 0, addr(z), None, addr(X), S)
         sdf = self.sdf_forward(addr(X), 3, M * sn0, keep=False, want_feat=False)['sdf']
         var = self.p['deviation_network.variance']
         zn, Xn = e(M, sn1), e(M * sn1, 3)
-        L.check(lib.nu_probe_weights(c_p(addr(pts)), c_p(addr(dirs)), c_p(addr(z)), c_p(addr(sdf)), M, sn0, c_p(addr(var)),
-                                     c_p(addr(uv)), sn1, c_p(addr(zn)), c_p(addr(Xn)), c_p(0), S), "nu_probe_weights")
+        lib.nu_probe_weights(addr(pts), addr(dirs), addr(z), addr(sdf), M, sn0, addr(var), addr(uv), sn1, addr(zn), addr(Xn), None, S)
         sdf2 = self.sdf_forward(addr(Xn), 3, M * sn1, keep=False, want_feat=False)['sdf']
         wsum = e(M)
-        L.check(lib.nu_probe_weights(c_p(addr(pts)), c_p(addr(dirs)), c_p(addr(zn)), c_p(addr(sdf2)), M, sn1,
-                                     c_p(addr(var)), c_p(0), 0, c_p(0), c_p(0), c_p(addr(wsum)), S), "nu_probe_weights")
+        lib.nu_probe_weights(addr(pts), addr(dirs), addr(zn), addr(sdf2), M, sn1, addr(var), None, 0, None, None, addr(wsum), S)
         return wsum
 
     def zero_stale_wgrads(self, which):

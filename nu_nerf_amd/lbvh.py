@@ -6,7 +6,6 @@ device->host->device round trips; `Scene` mirrors the part of `DiffRender.Scene`
 (network/DiffRender.py:318-360, :410-416, :539-549): angle-weighted vertex normals and the differentiable
 re-intersection (u, v, t, interpolated normal) of the hit triangles.
 """
-import ctypes
 import math
 
 import numpy as np
@@ -25,7 +24,6 @@ class LBVH:
     def __init__(self, vertices, faces):
         L.require_cuda(vertices, faces)
         self.lib = L.load()
-        self.lib.nu_lbvh_bytes.restype = ctypes.c_longlong
         self.V = vertices.detach().to(torch.float32).contiguous()
         self.F = faces.detach().to(torch.int32).contiguous()
         self.n_faces = int(self.F.shape[0])
@@ -33,8 +31,7 @@ class LBVH:
             raise EmptyMeshError("LBVH: the mesh has no triangles")
         nbytes = self.lib.nu_lbvh_bytes(self.n_faces)
         self.buf = torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=self.V.device)
-        L.check(self.lib.nu_lbvh_build(L.ptr(self.V), int(self.V.shape[0]), L.ptr(self.F), self.n_faces, L.ptr(self.buf),
-                                       ctypes.c_longlong(nbytes), L.stream()), "nu_lbvh_build")
+        self.lib.nu_lbvh_build(L.ptr(self.V), int(self.V.shape[0]), L.ptr(self.F), self.n_faces, L.ptr(self.buf), nbytes, L.stream())
 
     def intersect(self, ray, tmin=0.0, tmax=1e16, return_t=False):
         ray = ray.detach().to(torch.float32).contiguous()
@@ -42,8 +39,7 @@ class LBVH:
         hit = torch.empty(N, device=ray.device)
         idx = torch.empty(N, dtype=torch.int32, device=ray.device)
         t = torch.empty(N, device=ray.device) if return_t else None
-        L.check(self.lib.nu_lbvh_trace(L.ptr(self.buf), self.n_faces, L.ptr(ray), N, ctypes.c_float(tmin), ctypes.c_float(tmax),
-                                       L.ptr(hit), L.ptr(idx), L.ptr(t), L.stream()), "nu_lbvh_trace")
+        self.lib.nu_lbvh_trace(L.ptr(self.buf), self.n_faces, L.ptr(ray), N, tmin, tmax, L.ptr(hit), L.ptr(idx), L.ptr(t), L.stream())
         return (hit, idx, t) if return_t else (hit, idx)
 
     def intersect_brute(self, ray, tmin=0.0, tmax=1e16):
@@ -52,8 +48,8 @@ class LBVH:
         N = ray.shape[0]
         hit = torch.empty(N, device=ray.device)
         idx = torch.empty(N, dtype=torch.int32, device=ray.device)
-        L.check(self.lib.nu_brute_trace(L.ptr(self.V), L.ptr(self.F), self.n_faces, L.ptr(ray), N, ctypes.c_float(tmin),
-                                        ctypes.c_float(tmax), L.ptr(hit), L.ptr(idx), L.ptr(None), L.stream()), "nu_brute_trace")
+        self.lib.nu_brute_trace(L.ptr(self.V), L.ptr(self.F), self.n_faces, L.ptr(ray), N,
+                                tmin, tmax, L.ptr(hit), L.ptr(idx), L.ptr(None), L.stream())
         return hit, idx
 
     def _closest(self, fn, args, points, max_dist):
@@ -75,8 +71,7 @@ class LBVH:
             if not max_dist >= 0:
                 raise ValueError(f"closest_points: max_dist must be >= 0, got {max_dist}")
             max_d2 = float(max_dist) * float(max_dist)     # float64 square, rounded once to fp32 by the call
-        L.check(getattr(self.lib, fn)(*args, L.ptr(pts), N, ctypes.c_float(max_d2), L.ptr(d2), L.ptr(idx), L.ptr(closest),
-                                      L.stream()), fn)
+        getattr(self.lib, fn)(*args, L.ptr(pts), N, max_d2, L.ptr(d2), L.ptr(idx), L.ptr(closest), L.stream())
         return d2, idx, closest
 
     def closest_points(self, points, max_dist=None):

@@ -210,10 +210,8 @@ class _FusedLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rgb, acc, rgb_bg, spec_raw, gerr, nrm_sum, gt, cand, white_bg, exp_max, w_eik, w_reg, w_nrm, point_weight=None):
-        import ctypes
         from . import _lib as L
         lib = L.load()
-        lib.nu_loss_workspace_bytes.restype = ctypes.c_longlong
         L.require_cuda(rgb, acc, rgb_bg, spec_raw, gt)
         dev = rgb.device
         R, P = rgb.shape[0], gerr.shape[0]
@@ -226,10 +224,9 @@ class _FusedLossFn(torch.autograd.Function):
         ws = torch.empty((nb + 3) // 4, device=dev)
         ray_rgb, color_spec, loss_rgb, terms = (torch.empty(R, 3, device=dev), torch.empty(R, 3, device=dev),
                                                 torch.empty(R, device=dev), torch.empty(6, device=dev))
-        L.check(lib.nu_loss_fwd(L.ptr(rgb_), L.ptr(acc_), L.ptr(bg_), L.ptr(spec_), L.ptr(gerr_ if P else None), L.ptr(nrm_), L.ptr(gt_),
-                                L.ptr(cand_), R, P, int(white_bg), ctypes.c_float(exp_max), ctypes.c_float(w_eik), ctypes.c_float(w_reg),
-                                ctypes.c_float(w_nrm), L.ptr(ray_rgb), L.ptr(color_spec), L.ptr(loss_rgb), L.ptr(terms), L.ptr(pw_), L.ptr(ws),
-                                ctypes.c_longlong(nb), L.stream()), "nu_loss_fwd")
+        lib.nu_loss_fwd(L.ptr(rgb_), L.ptr(acc_), L.ptr(bg_), L.ptr(spec_), L.ptr(gerr_ if P else None), L.ptr(nrm_),
+                        L.ptr(gt_), L.ptr(cand_), R, P, int(white_bg), exp_max, w_eik, w_reg, w_nrm, L.ptr(ray_rgb),
+                        L.ptr(color_spec), L.ptr(loss_rgb), L.ptr(terms), L.ptr(pw_), L.ptr(ws), nb, L.stream())
         ctx.save_for_backward(rgb_, acc_, bg_, spec_, gt_, ray_rgb, color_spec, loss_rgb, terms)
         ctx.cand, ctx.nrm, ctx.pw = cand_, nrm_ is not None, pw_
         ctx.k = (R, P, int(white_bg), float(exp_max), float(w_eik), float(w_reg), float(w_nrm))
@@ -238,7 +235,6 @@ class _FusedLossFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_total, *_):
-        import ctypes
         from . import _lib as L
         lib = L.load()
         rgb_, acc_, bg_, spec_, gt_, ray_rgb, color_spec, loss_rgb, terms = ctx.saved_tensors
@@ -249,10 +245,9 @@ class _FusedLossFn(torch.autograd.Function):
                                       torch.empty(R, 3, device=dev))
         d_gerr = torch.empty(P, device=dev)
         d_nrm = torch.empty(R, device=dev) if ctx.nrm else None
-        L.check(lib.nu_loss_bwd(L.ptr(rgb_), L.ptr(acc_), L.ptr(bg_), L.ptr(spec_), L.ptr(gt_), L.ptr(ctx.cand), L.ptr(ray_rgb),
-                                L.ptr(color_spec), L.ptr(loss_rgb), L.ptr(terms), L.ptr(up), L.ptr(ctx.pw), R, P, white_bg, ctypes.c_float(exp_max),
-                                ctypes.c_float(w_eik), ctypes.c_float(w_reg), ctypes.c_float(w_nrm), L.ptr(d_rgb), L.ptr(d_acc),
-                                L.ptr(d_bg), L.ptr(d_spec), L.ptr(d_gerr if P else None), L.ptr(d_nrm), L.stream()), "nu_loss_bwd")
+        lib.nu_loss_bwd(L.ptr(rgb_), L.ptr(acc_), L.ptr(bg_), L.ptr(spec_), L.ptr(gt_), L.ptr(ctx.cand), L.ptr(ray_rgb), L.ptr(color_spec),
+                        L.ptr(loss_rgb), L.ptr(terms), L.ptr(up), L.ptr(ctx.pw), R, P, white_bg, exp_max, w_eik, w_reg, w_nrm,
+                        L.ptr(d_rgb), L.ptr(d_acc), L.ptr(d_bg), L.ptr(d_spec), L.ptr(d_gerr if P else None), L.ptr(d_nrm), L.stream())
         return d_rgb, d_acc, d_bg, d_spec, d_gerr, d_nrm, None, None, None, None, None, None, None, None
 
 

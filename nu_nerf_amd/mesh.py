@@ -17,15 +17,11 @@ normal points inside, which is where the reference's raw PyMCubes output of an s
 extract_mesh_stage1.py:40 -- after np.fliplr the normals point outward.  Every entry runs on the caller's current stream and syncs
 the host once (the sizes of the outputs), plus once per sdf_grid (the row counts of its slabs).
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib as L
 from .engine import addr
-
-c_p, c_ll, c_f = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_float
 
 # grid points per slab of sdf_grid: the no-grad layered SDF forward holds ~3.3 KB of activations per evaluated row, so 2^19 points
 # keep a slab under ~1.8 GB even when every point is inside the unit sphere
@@ -34,15 +30,11 @@ _BRICK = 256
 
 
 def _lib():
-    lib = L.load()
-    lib.nu_mc_workspace_bytes.restype = c_ll
-    return lib
+    return L.load()
 
 
 def _workspace(lib, dev, nx, ny, nz):
-    nbytes = int(lib.nu_mc_workspace_bytes(nx, ny, nz))
-    if nbytes < 0:
-        raise L.NuNerfLibraryError(f"nu_mc_workspace_bytes({nx}, {ny}, {nz}) failed with code {nbytes}")
+    nbytes = lib.nu_mc_workspace_bytes(nx, ny, nz)
     return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev), nbytes
 
 
@@ -64,13 +56,13 @@ def _mc_device(u, threshold):
     lib = _lib()
     dev = u.device
     nx, ny, nz = (int(s) for s in u.shape)
-    iso = c_f(float(threshold))
+    iso = float(threshold)
     with torch.cuda.device(dev):
         S = L.stream(dev.index)
         ws, nbytes = _workspace(lib, dev, nx, ny, nz)
         tot = torch.empty(2, dtype=torch.int64, device=dev)
-        L.check(lib.nu_mc_count(c_p(addr(u)), nx, ny, nz, iso, c_p(addr(ws)), c_ll(nbytes), S), "nu_mc_count")
-        L.check(lib.nu_mc_scan(nx, ny, nz, c_p(addr(ws)), c_ll(nbytes), c_p(addr(tot)), S), "nu_mc_scan")
+        lib.nu_mc_count(addr(u), nx, ny, nz, iso, addr(ws), nbytes, S)
+        lib.nu_mc_scan(nx, ny, nz, addr(ws), nbytes, addr(tot), S)
         nv, nf = (int(x) for x in tot.cpu())                  # the one host sync: sizes of the outputs
         if nv >= 2 ** 31:
             raise ValueError(f"marching_cubes: {nv} vertices do not fit int32 face indices")
@@ -79,10 +71,8 @@ def _mc_device(u, threshold):
         if nv == 0:
             return V, F
         first_vid = torch.empty(nx * ny * nz, dtype=torch.int32, device=dev)   # written at the owners only (read at the owners only)
-        L.check(lib.nu_mc_write_vertices(c_p(addr(u)), nx, ny, nz, iso, c_p(addr(ws)), c_ll(nbytes), c_p(addr(V)),
-                                         c_p(addr(first_vid)), S), "nu_mc_write_vertices")
-        L.check(lib.nu_mc_write_triangles(c_p(addr(u)), nx, ny, nz, iso, c_p(addr(ws)), c_ll(nbytes), c_p(addr(first_vid)),
-                                          c_p(addr(F)), S), "nu_mc_write_triangles")
+        lib.nu_mc_write_vertices(addr(u), nx, ny, nz, iso, addr(ws), nbytes, addr(V), addr(first_vid), S)
+        lib.nu_mc_write_triangles(addr(u), nx, ny, nz, iso, addr(ws), nbytes, addr(first_vid), addr(F), S)
     return V, F
 
 
@@ -126,8 +116,7 @@ def sdf_grid(engine, bmin, bmax, res, outside_val=1.0, slab_points=None, stats=N
         ws, nbytes = _workspace(lib, dev, res, res, res)
         nslab = (npts + slab - 1) // slab
         rows_at = torch.empty(nslab + 1, dtype=torch.int64, device=dev)
-        L.check(lib.nu_grid_inside_count(c_p(addr(X)), c_p(addr(Y)), c_p(addr(Z)), res, res, res, c_ll(slab), c_p(addr(ws)),
-                                         c_ll(nbytes), c_p(addr(rows_at)), S), "nu_grid_inside_count")
+        lib.nu_grid_inside_count(addr(X), addr(Y), addr(Z), res, res, res, slab, addr(ws), nbytes, addr(rows_at), S)
         rows_at = rows_at.cpu().tolist()                           # the one host sync: row counts of every slab
         if stats is not None:
             stats.update(points=rows_at[-1], slabs=nslab)
@@ -139,11 +128,10 @@ def sdf_grid(engine, bmin, bmax, res, outside_val=1.0, slab_points=None, stats=N
             sdf = None
             if P > 0:
                 rows = engine.empty(P, 3)
-                L.check(lib.nu_grid_compact(c_p(addr(X)), c_p(addr(Y)), c_p(addr(Z)), res, res, res, c_ll(p0), c_ll(n), c_p(addr(ws)),
-                                            c_ll(nbytes), c_p(addr(rows)), S), "nu_grid_compact")
+                lib.nu_grid_compact(addr(X), addr(Y), addr(Z), res, res, res, p0, n, addr(ws), nbytes, addr(rows), S)
                 sdf = engine.sdf_forward(addr(rows), 3, P, keep=False, want_feat=False)['sdf']
-            L.check(lib.nu_grid_scatter(c_p(addr(X)), c_p(addr(Y)), c_p(addr(Z)), res, res, res, c_ll(p0), c_ll(n), c_p(addr(ws)),
-                                        c_ll(nbytes), c_p(addr(sdf)), c_f(float(outside_val)), c_p(addr(u)), S), "nu_grid_scatter")
+            lib.nu_grid_scatter(addr(X), addr(Y), addr(Z), res, res, res, p0, n, addr(ws),
+                                nbytes, addr(sdf), float(outside_val), addr(u), S)
     return u
 
 

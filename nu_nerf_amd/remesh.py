@@ -18,7 +18,6 @@ Every step runs on the caller's current stream; the host reads only counts (one 
 bits.
 """
 import argparse
-import ctypes
 import math
 import os
 import sys
@@ -27,8 +26,6 @@ import numpy as np
 import torch
 
 from . import _lib as L
-
-c_p, c_f = ctypes.c_void_p, ctypes.c_float
 
 MAX_COLLAPSE_ROUNDS = 64          # collapse rounds per pass (each round is an independent set of collapses)
 MAX_FLIP_ROUNDS = 32              # flip rounds per pass
@@ -48,7 +45,7 @@ def _lib():
 
 
 def _p(t):
-    return c_p(t.data_ptr())
+    return t.data_ptr()
 
 
 class Tables:
@@ -62,14 +59,13 @@ class Tables:
         nh = 3 * self.nf
         dev = V.device
         keys = torch.empty(nh, dtype=torch.int64, device=dev)
-        L.check(lib.nu_rm_edge_keys(_p(F), self.nf, _p(keys), S), "nu_rm_edge_keys")
+        lib.nu_rm_edge_keys(_p(F), self.nf, _p(keys), S)
         skeys, perm = torch.sort(keys, stable=True)
         self.E = torch.empty(nh, 4, dtype=torch.int32, device=dev)
         self.he_edge = torch.empty(nh, dtype=torch.int32, device=dev)
         self.vlock = torch.empty(self.nv, dtype=torch.uint8, device=dev)
         self.vbound = torch.empty(self.nv, dtype=torch.uint8, device=dev)
-        L.check(lib.nu_rm_edges(_p(F), self.nf, self.nv, _p(skeys), _p(perm), _p(self.E), _p(self.he_edge), _p(self.vlock),
-                                _p(self.vbound), S), "nu_rm_edges")
+        lib.nu_rm_edges(_p(F), self.nf, self.nv, _p(skeys), _p(perm), _p(self.E), _p(self.he_edge), _p(self.vlock), _p(self.vbound), S)
         svid, cperm = torch.sort(F.reshape(-1), stable=True)
         self.vc_off = torch.searchsorted(svid, torch.arange(self.nv + 1, dtype=torch.int32, device=dev)).to(torch.int32)
         self.vc_corner = cperm.to(torch.int32)
@@ -87,7 +83,7 @@ def split(V, F, max_len2):
     nh = 3 * T.nf
     eflag = torch.empty(nh, dtype=torch.int32, device=V.device)
     fcnt = torch.empty(T.nf, dtype=torch.int32, device=V.device)
-    L.check(lib.nu_rm_split_count(_p(V), _p(F), T.nf, _p(T.E), _p(T.he_edge), c_f(max_len2), _p(eflag), _p(fcnt), S), "nu_rm_split_count")
+    lib.nu_rm_split_count(_p(V), _p(F), T.nf, _p(T.E), _p(T.he_edge), max_len2, _p(eflag), _p(fcnt), S)
     vinc, finc = torch.cumsum(eflag, 0), torch.cumsum(fcnt, 0)
     ns, nfo = (int(x) for x in torch.stack([vinc[-1], finc[-1]]).cpu())      # the pass's one host read
     if ns == 0:
@@ -95,8 +91,7 @@ def split(V, F, max_len2):
     Vo = torch.empty(T.nv + ns, 3, dtype=torch.float32, device=V.device)
     Fo = torch.empty(nfo, 3, dtype=torch.int32, device=V.device)
     voff, foff = vinc - eflag, finc - fcnt          # named: a temporary would be freed before the kernel reads it
-    L.check(lib.nu_rm_split_write(_p(V), T.nv, _p(F), T.nf, _p(T.E), _p(T.he_edge), _p(eflag), _p(voff), _p(foff), _p(Vo), _p(Fo), S),
-            "nu_rm_split_write")
+    lib.nu_rm_split_write(_p(V), T.nv, _p(F), T.nf, _p(T.E), _p(T.he_edge), _p(eflag), _p(voff), _p(foff), _p(Vo), _p(Fo), S)
     return Vo, Fo, ns
 
 
@@ -111,7 +106,7 @@ class _Round:
         nh = 3 * self.T.nf
         self.npts = torch.empty(nh, dtype=torch.int32, device=V.device)
         fn = getattr(self.lib, f"nu_rm_{kind}_count")
-        L.check(fn(*self.T.args(), *(c_f(x) for x in params), _p(self.npts), self.S), f"nu_rm_{kind}_count")
+        fn(*self.T.args(), *params, _p(self.npts), self.S)
         self.inc = torch.cumsum(self.npts, 0)
 
     def winners(self, total, bvh, max_d2):
@@ -120,27 +115,25 @@ class _Round:
         nh = 3 * T.nf
         poff = self.inc - self.npts
         pts = torch.empty(max(total, 1), 3, dtype=torch.float32, device=dev)
-        L.check(getattr(self.lib, f"nu_rm_{self.kind}_points")(*T.args(), *(c_f(x) for x in self.params), _p(self.npts), _p(poff),
-                                                              _p(pts), self.S), f"nu_rm_{self.kind}_points")
+        getattr(self.lib, f"nu_rm_{self.kind}_points")(*T.args(), *self.params, _p(self.npts), _p(poff), _p(pts), self.S)
         d2 = torch.empty(total, dtype=torch.float32, device=dev)
         idx = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
         if total > 0:
-            L.check(self.lib.nu_lbvh_closest(_p(bvh.buf), bvh.n_faces, _p(pts), total, c_f(max_d2), _p(d2), _p(idx), c_p(0), self.S),
-                    "nu_lbvh_closest")
+            self.lib.nu_lbvh_closest(_p(bvh.buf), bvh.n_faces, _p(pts), total, max_d2, _p(d2), _p(idx), None, self.S)
         ckey = torch.empty(nh, dtype=torch.int64, device=dev)
         claim = torch.empty(T.nv, dtype=torch.int64, device=dev)
         win = torch.empty(nh, dtype=torch.int32, device=dev)
-        extra = (c_f(self.params[0]),) if self.kind == 'flip' else ()
-        L.check(getattr(self.lib, f"nu_rm_{self.kind}_claim")(*T.args(), *extra, _p(self.npts), _p(poff), _p(idx), _p(ckey), _p(claim),
-                                                             _p(win), self.S), f"nu_rm_{self.kind}_claim")
+        extra = self.params[:1] if self.kind == 'flip' else ()
+        getattr(self.lib, f"nu_rm_{self.kind}_claim")(*T.args(), *extra, _p(self.npts), _p(poff),
+                                                      _p(idx), _p(ckey), _p(claim), _p(win), self.S)
         return win
 
     def apply(self, win):
         T = self.T
         if self.kind == 'collapse':
-            L.check(self.lib.nu_rm_collapse_apply(*T.args(), _p(win), _p(T.V), _p(T.F), self.S), "nu_rm_collapse_apply")
+            self.lib.nu_rm_collapse_apply(*T.args(), _p(win), _p(T.V), _p(T.F), self.S)
         else:
-            L.check(self.lib.nu_rm_flip_apply(*T.args(), _p(win), _p(T.F), self.S), "nu_rm_flip_apply")
+            self.lib.nu_rm_flip_apply(*T.args(), _p(win), _p(T.F), self.S)
 
 
 def _rounds(kind, V, F, params, bvh, max_d2, max_rounds):
@@ -189,7 +182,7 @@ def relax(V, F, T=None):
     """Tangential relaxation (Jacobi) of every unlocked vertex.  T: the Tables of (V, F), when the caller has them."""
     T = T or Tables(V, F)
     out = torch.empty_like(V)
-    L.check(_lib().nu_rm_relax(*T.args(), _p(out), L.stream(V.device.index)), "nu_rm_relax")
+    _lib().nu_rm_relax(*T.args(), _p(out), L.stream(V.device.index))
     return out
 
 
@@ -202,8 +195,8 @@ def project(V, F, bvh, T=None):
     q = torch.empty(nv, 3, dtype=torch.float32, device=V.device)
     out = torch.empty_like(V)
     lib, S = _lib(), L.stream(V.device.index)
-    L.check(lib.nu_lbvh_closest(_p(bvh.buf), bvh.n_faces, _p(V), nv, c_f(math.inf), _p(d2), _p(idx), _p(q), S), "nu_lbvh_closest")
-    L.check(lib.nu_rm_project(_p(V), nv, _p(T.vlock), _p(q), _p(out), S), "nu_rm_project")
+    lib.nu_lbvh_closest(_p(bvh.buf), bvh.n_faces, _p(V), nv, math.inf, _p(d2), _p(idx), _p(q), S)
+    lib.nu_rm_project(_p(V), nv, _p(T.vlock), _p(q), _p(out), S)
     return out
 
 

@@ -16,7 +16,6 @@ the learned index of refraction:
 torch is left with index bookkeeping (one nonzero per mask, index_select / index_add) and O(rays) glue.
 state_dict() names/order equal the reference's (574 entries incl. the `color_network.stage1_network.*` aliases).
 """
-import ctypes
 import os
 
 import numpy as np
@@ -24,7 +23,6 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib as L
 from . import stage2_ops as O
 from . import torch_glue as G
 from .engine import Stage1Engine, addr
@@ -228,7 +226,6 @@ class Stage2Renderer(nn.Module):
         eng = n2.eng
         lib, S = eng.lib, eng.stream()
         M, dev = start.shape[0], start.device
-        cp = ctypes.c_void_p
         zn = torch.linspace(0, 1, 64, device=dev)
         pts = (start[:, None, :] + (end - start)[:, None, :] * zn[None, :, None]).reshape(-1, 3).contiguous()
         sdf = eng.sdf_forward(addr(pts), 3, M * 64, keep=False, want_feat=False)['sdf']
@@ -241,14 +238,12 @@ class Stage2Renderer(nn.Module):
         sn = 64
         for it in range(2):
             zn_new, Xn = eng.empty(M, 32), eng.empty(M * 32, 3)
-            L.check(lib.nu_upsample(cp(addr(o)), cp(addr(d)), cp(addr(z)), cp(addr(sdf)), M, sn, cp(addr(var)),
-                                    ctypes.c_float(64.0 * 2 ** it), 1 if self.cfg['clip_sample_variance'] else 0,
-                                    cp(addr(uv)), 32, cp(addr(zn_new)), cp(addr(Xn)), S), "nu_upsample")
+            lib.nu_upsample(addr(o), addr(d), addr(z), addr(sdf), M, sn, addr(var), 64.0 * 2 ** it,
+                            1 if self.cfg['clip_sample_variance'] else 0, addr(uv), 32, addr(zn_new), addr(Xn), S)
             last = it == 1
             sdf_n = None if last else eng.sdf_forward(addr(Xn), 3, M * 32, keep=False, want_feat=False)['sdf']
             zo, so = eng.empty(M, sn + 32), (None if last else eng.empty(M, sn + 32))
-            L.check(lib.nu_merge_sorted(cp(addr(z)), cp(addr(sdf)), sn, cp(addr(zn_new)), cp(addr(sdf_n)), 32, M,
-                                        cp(addr(zo)), cp(addr(so)), S), "nu_merge_sorted")
+            lib.nu_merge_sorted(addr(z), addr(sdf), sn, addr(zn_new), addr(sdf_n), 32, M, addr(zo), addr(so), S)
             z, sdf, sn = zo, so, sn + 32
         return z
 

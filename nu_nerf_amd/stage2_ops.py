@@ -11,15 +11,10 @@
 
 A segment is (start [N,3], v [N,3], z [N,S1]): nodes x_j = start + v * z_j, z without gradient (csrc/stage2.hip).
 """
-import ctypes
-
 import torch
 
-from . import _lib as L
 from .engine import addr
 from .nets import _token_grad
-
-c_p = ctypes.c_void_p
 
 
 class _OuterSegmentsFn(torch.autograd.Function):
@@ -41,8 +36,7 @@ class _OuterSegmentsFn(torch.autograd.Function):
             cnt, off = torch.empty(max(n, 1), dtype=torch.int32, device=dev), torch.empty(max(n, 1), dtype=torch.int32, device=dev)
             offs.append(off)
             if n > 0:
-                L.check(lib.nu_s2_seg_count(c_p(addr(st)), c_p(addr(v)), c_p(addr(z)), n, s1, c_p(addr(cnt)), c_p(addr(off)),
-                                            c_p(addr(totals, i)), S_), "nu_s2_seg_count")
+                lib.nu_s2_seg_count(addr(st), addr(v), addr(z), n, s1, addr(cnt), addr(off), addr(totals, i), S_)
         P_seg = [int(x) for x in totals.tolist()]          # the one device -> host read of the pass (buffer sizes)
         P = sum(P_seg)
         pt = eng.empty(max(P, 1), 8)
@@ -50,8 +44,8 @@ class _OuterSegmentsFn(torch.autograd.Function):
         pbase = 0
         for i, ((st, v, z, d), (n, s1)) in enumerate(zip(segs, dims)):
             if n > 0:
-                L.check(lib.nu_s2_seg_write(c_p(addr(st)), c_p(addr(v)), c_p(addr(z)), c_p(addr(d)), n, s1, c_p(addr(offs[i])), pbase,
-                                            row_base[i], c_p(addr(pt)), c_p(addr(idx)), c_p(addr(pos)), S_), "nu_s2_seg_write")
+                lib.nu_s2_seg_write(addr(st), addr(v), addr(z), addr(d), n, s1, addr(offs[i]),
+                                    pbase, row_base[i], addr(pt), addr(idx), addr(pos), S_)
             pbase += P_seg[i]
         b = eng.nerf_forward(pt[:P], idx, P, alpha_all, color_all) if P > 0 else None
         ctx.eng, ctx.names, ctx.segs, ctx.dims, ctx.row_base = eng, names, segs, dims, row_base
@@ -72,16 +66,14 @@ class _OuterSegmentsFn(torch.autograd.Function):
             da = dalpha.contiguous() if dalpha is not None else eng.zeros(tot_rows)
             dc = dcolor.contiguous() if dcolor is not None else eng.zeros(tot_rows, 4)
             ddist, dx, dd = eng.empty(P), eng.empty(P, 3), eng.empty(P, 3)
-            L.check(lib.nu_s2_ddist(c_p(addr(ctx.b['sig'])), c_p(addr(pt)), c_p(addr(idx)), P, c_p(addr(da)), c_p(addr(ddist)), S_),
-                    "nu_s2_ddist")
+            lib.nu_s2_ddist(addr(ctx.b['sig']), addr(pt), addr(idx), P, addr(da), addr(ddist), S_)
             eng.nerf_backward(ctx.b, pt[:P], idx, da, dc, flat, dx=dx, ddir=dd)
             eng.unpack_grads(flat, eng.nerf_all)
         for i, ((st, v, z, d), (n, s1)) in enumerate(zip(segs, dims)):
             gs, gv, gd = torch.zeros_like(st), torch.zeros_like(v), torch.zeros_like(d)
             if n > 0 and P > 0:
-                L.check(lib.nu_s2_seg_bwd(c_p(addr(st)), c_p(addr(v)), c_p(addr(z)), n, s1, ctx.row_base[i], c_p(addr(ctx.pos)),
-                                          c_p(addr(dx)), c_p(addr(ddist)), c_p(addr(dd)), c_p(addr(gs)), c_p(addr(gv)), c_p(addr(gd)), S_),
-                        "nu_s2_seg_bwd")
+                lib.nu_s2_seg_bwd(addr(st), addr(v), addr(z), n, s1, ctx.row_base[i], addr(ctx.pos),
+                                  addr(dx), addr(ddist), addr(dd), addr(gs), addr(gv), addr(gd), S_)
             out += [gs, gv, None, gd]
         ctx.b = None
         return (None, None, None, _token_grad(eng, flat, ctx.names)) + tuple(out)
@@ -109,8 +101,7 @@ class _CompositeFn(torch.autograd.Function):
         N, S = alpha.shape
         out, Tout = torch.empty(N, 3, device=alpha.device), torch.empty(N, 3, device=alpha.device)
         if N > 0:
-            L.check(eng.lib.nu_s2_composite_fwd(c_p(addr(alpha)), c_p(addr(color)), c_p(addr(T)), N, S, c_p(addr(out)), c_p(addr(Tout)),
-                                                eng.stream()), "nu_s2_composite_fwd")
+            eng.lib.nu_s2_composite_fwd(addr(alpha), addr(color), addr(T), N, S, addr(out), addr(Tout), eng.stream())
         ctx.eng = eng
         ctx.save_for_backward(alpha, color, T)
         ctx.set_materialize_grads(False)
@@ -126,10 +117,8 @@ class _CompositeFn(torch.autograd.Function):
         dout_c = dout.contiguous() if dout is not None else None
         dTout_c = dTout.contiguous() if dTout is not None else None
         if N > 0:
-            L.check(ctx.eng.lib.nu_s2_composite_bwd(c_p(addr(alpha)), c_p(addr(color)), c_p(addr(T)), N, S,
-                                                    c_p(addr(dout_c)), c_p(addr(dTout_c)),
-                                                    c_p(addr(dalpha)), c_p(addr(dcolor)), c_p(addr(dT)), ctx.eng.stream()),
-                    "nu_s2_composite_bwd")
+            ctx.eng.lib.nu_s2_composite_bwd(addr(alpha), addr(color), addr(T), N, S, addr(dout_c), addr(dTout_c),
+                                            addr(dalpha), addr(dcolor), addr(dT), ctx.eng.stream())
         return None, dalpha, dcolor, dT
 
 
@@ -146,8 +135,8 @@ class _RefractFn(torch.autograd.Function):
         dev = d.device
         flag = torch.empty(M, dtype=torch.uint8, device=dev)             # (the kernels write every row of every output)
         eta, nd, ns = torch.empty(M, device=dev), torch.empty(M, 3, device=dev), torch.empty(M, 3, device=dev)
-        L.check(eng.lib.nu_s2_refract_fwd(c_p(addr(d)), c_p(addr(nrm)), c_p(addr(ior)), c_p(addr(point)), M, 1 if outside else 0,
-                                          c_p(addr(flag)), c_p(addr(eta)), c_p(addr(nd)), c_p(addr(ns)), eng.stream()), "nu_s2_refract_fwd")
+        eng.lib.nu_s2_refract_fwd(addr(d), addr(nrm), addr(ior), addr(point), M, 1 if outside else 0,
+                                  addr(flag), addr(eta), addr(nd), addr(ns), eng.stream())
         ctx.eng, ctx.outside = eng, outside
         ctx.save_for_backward(d, nrm, ior)
         ctx.mark_non_differentiable(flag)
@@ -161,9 +150,8 @@ class _RefractFn(torch.autograd.Function):
         dd, dn, dior, dpoint = torch.empty_like(d), torch.empty_like(nrm), torch.empty_like(ior), torch.empty_like(d)
         cg = lambda t: t.contiguous() if t is not None else None
         g_eta, g_nd, g_ns = cg(g_eta), cg(g_nd), cg(g_ns)
-        L.check(ctx.eng.lib.nu_s2_refract_bwd(c_p(addr(d)), c_p(addr(nrm)), c_p(addr(ior)), M, 1 if ctx.outside else 0, c_p(addr(g_nd)),
-                                              c_p(addr(g_ns)), c_p(addr(g_eta)), c_p(addr(dd)), c_p(addr(dn)), c_p(addr(dior)),
-                                              c_p(addr(dpoint)), ctx.eng.stream()), "nu_s2_refract_bwd")
+        ctx.eng.lib.nu_s2_refract_bwd(addr(d), addr(nrm), addr(ior), M, 1 if ctx.outside else 0, addr(g_nd), addr(g_ns),
+                                      addr(g_eta), addr(dd), addr(dn), addr(dior), addr(dpoint), ctx.eng.stream())
         return None, dd, dn, dior, dpoint, None
 
 
@@ -182,9 +170,8 @@ class _ShellFn(torch.autograd.Function):
         refr, ok = (torch.empty(M, dtype=torch.uint8, device=dev) for _ in range(2))   # (the kernels write every row of every output)
         eta = torch.empty(M, device=dev)
         nrm, pend, ns, nd = (torch.empty(M, 3, device=dev) for _ in range(4))
-        L.check(eng.lib.nu_s2_shell_fwd(c_p(addr(d)), c_p(addr(nraw)), c_p(addr(point)), c_p(addr(ior_raw)), c_p(addr(gk)), c_p(addr(th_raw)),
-                                        M, 1 if inside else 0, c_p(addr(refr)), c_p(addr(ok)), c_p(addr(eta)), c_p(addr(nrm)),
-                                        c_p(addr(pend)), c_p(addr(ns)), c_p(addr(nd)), eng.stream()), "nu_s2_shell_fwd")
+        eng.lib.nu_s2_shell_fwd(addr(d), addr(nraw), addr(point), addr(ior_raw), addr(gk), addr(th_raw), M, 1 if inside else 0,
+                                addr(refr), addr(ok), addr(eta), addr(nrm), addr(pend), addr(ns), addr(nd), eng.stream())
         ctx.eng, ctx.inside = eng, inside
         ctx.save_for_backward(d, nraw, point, ior_raw, gk, th_raw)
         ctx.mark_non_differentiable(refr, ok, eta)
@@ -199,10 +186,9 @@ class _ShellFn(torch.autograd.Function):
         g_i, g_k, g_t = (torch.empty_like(gk) for _ in range(3))
         cg = lambda t: t.contiguous() if t is not None else None
         g_nrm, g_pend, g_ns, g_nd = cg(g_nrm), cg(g_pend), cg(g_ns), cg(g_nd)
-        L.check(ctx.eng.lib.nu_s2_shell_bwd(c_p(addr(d)), c_p(addr(nraw)), c_p(addr(point)), c_p(addr(ior_raw)), c_p(addr(gk)),
-                                            c_p(addr(th_raw)), M, 1 if ctx.inside else 0, c_p(addr(g_nrm)), c_p(addr(g_pend)),
-                                            c_p(addr(g_ns)), c_p(addr(g_nd)), c_p(addr(g_d)), c_p(addr(g_n)), c_p(addr(g_p)), c_p(addr(g_i)),
-                                            c_p(addr(g_k)), c_p(addr(g_t)), ctx.eng.stream()), "nu_s2_shell_bwd")
+        ctx.eng.lib.nu_s2_shell_bwd(addr(d), addr(nraw), addr(point), addr(ior_raw), addr(gk), addr(th_raw), M,
+                                    1 if ctx.inside else 0, addr(g_nrm), addr(g_pend), addr(g_ns), addr(g_nd),
+                                    addr(g_d), addr(g_n), addr(g_p), addr(g_i), addr(g_k), addr(g_t), ctx.eng.stream())
         return None, g_d, g_n, g_p, g_i, g_k, g_t, None
 
 
@@ -222,9 +208,8 @@ class _HitFn(torch.autograd.Function):
         M = o.shape[0]
         point, nrm, t = torch.empty_like(o), torch.empty_like(o), torch.empty(M, device=o.device)
         gk = torch.empty(M, device=o.device) if vcurv is not None else torch.zeros(M, device=o.device)
-        L.check(eng.lib.nu_s2_hit_fwd(c_p(addr(o)), c_p(addr(d)), c_p(addr(face)), c_p(addr(verts)), c_p(addr(vnrm)), c_p(addr(faces)), M,
-                                      c_p(addr(point)), c_p(addr(nrm)), c_p(addr(t)), c_p(addr(vcurv)), c_p(addr(gk)), eng.stream()),
-                "nu_s2_hit_fwd")
+        eng.lib.nu_s2_hit_fwd(addr(o), addr(d), addr(face), addr(verts), addr(vnrm), addr(faces), M,
+                              addr(point), addr(nrm), addr(t), addr(vcurv), addr(gk), eng.stream())
         ctx.eng, ctx.consts = eng, (face, verts, vnrm, faces, vcurv)
         ctx.save_for_backward(o, d)
         ctx.set_materialize_grads(False)
@@ -238,9 +223,8 @@ class _HitFn(torch.autograd.Function):
         g_o, g_d = torch.empty_like(o), torch.empty_like(d)
         cg = lambda t: t.contiguous() if t is not None else None
         g_point, g_nrm, g_t, g_gk = cg(g_point), cg(g_nrm), cg(g_t), cg(g_gk)
-        L.check(ctx.eng.lib.nu_s2_hit_bwd(c_p(addr(o)), c_p(addr(d)), c_p(addr(face)), c_p(addr(verts)), c_p(addr(vnrm)), c_p(addr(faces)), M,
-                                          c_p(addr(g_point)), c_p(addr(g_nrm)), c_p(addr(g_t)), c_p(addr(g_o)), c_p(addr(g_d)),
-                                          c_p(addr(vcurv)), c_p(addr(g_gk if vcurv is not None else None)), ctx.eng.stream()), "nu_s2_hit_bwd")
+        ctx.eng.lib.nu_s2_hit_bwd(addr(o), addr(d), addr(face), addr(verts), addr(vnrm), addr(faces), M, addr(g_point), addr(g_nrm),
+                                  addr(g_t), addr(g_o), addr(g_d), addr(vcurv), addr(g_gk if vcurv is not None else None), ctx.eng.stream())
         return None, g_o, g_d, None, None, None, None, None
 
 
@@ -265,11 +249,10 @@ def far_importance_nodes(eng, start, dirs):
     start, dirs = start.detach().contiguous(), dirs.detach().contiguous()
     P = M * 192
     pt, idx = eng.empty(P, 8), torch.empty(P, dtype=torch.int32, device=dev)
-    L.check(lib.nu_s2_far_points(c_p(addr(start)), c_p(addr(dirs)), c_p(addr(zo)), M, 192, c_p(addr(pt)), c_p(addr(idx)), S_),
-            "nu_s2_far_points")
+    lib.nu_s2_far_points(addr(start), addr(dirs), addr(zo), M, 192, addr(pt), addr(idx), S_)
     alpha, color = eng.empty(P), eng.empty(P, 4)
     eng.nerf_forward(pt, idx, P, alpha, color)
-    L.check(lib.nu_s2_far_resample(c_p(addr(alpha)), c_p(addr(zo)), M, 192, 64, c_p(addr(zout)), S_), "nu_s2_far_resample")
+    lib.nu_s2_far_resample(addr(alpha), addr(zo), M, 192, 64, addr(zout), S_)
     return zout
 
 
@@ -284,9 +267,8 @@ class _ShadeEncodeFn(torch.autograd.Function):
         OL, IL, IW = torch.empty(3 * P, ld_ol, device=dev), torch.empty(2 * P, 128, device=dev), torch.empty(P, 96, device=dev)
         RL = torch.empty(P, ld_rl, device=dev) if refrac_freq >= 0 else None
         SD = torch.empty(P, 12, device=dev)
-        L.check(eng.lib.nu_s2_shade_encode_fwd(c_p(addr(x)), c_p(addr(nrm)), c_p(addr(view)), c_p(addr(m)), m.shape[1], P, 1 if sphere else 0,
-                                               pos_freq, ld_ol, refrac_freq, ld_rl, c_p(addr(OL)), c_p(addr(IL)), c_p(addr(IW)), c_p(addr(RL)),
-                                               c_p(addr(SD)), eng.stream()), "nu_s2_shade_encode_fwd")
+        eng.lib.nu_s2_shade_encode_fwd(addr(x), addr(nrm), addr(view), addr(m), m.shape[1], P, 1 if sphere else 0, pos_freq,
+                                       ld_ol, refrac_freq, ld_rl, addr(OL), addr(IL), addr(IW), addr(RL), addr(SD), eng.stream())
         ctx.eng, ctx.k = eng, (sphere, pos_freq, refrac_freq, ld_ol, ld_rl, m.shape[1])
         ctx.save_for_backward(x, nrm, view, SD)
         ctx.mark_non_differentiable(IW, SD)
@@ -307,10 +289,9 @@ class _ShadeEncodeFn(torch.autograd.Function):
         cg = lambda t: t.contiguous() if t is not None else None
         dOL, dIL, dnov = cg(dOL), cg(dIL), cg(dnov)
         dRL = cg(dRL) if refrac_freq >= 0 else None
-        L.check(ctx.eng.lib.nu_s2_shade_encode_bwd(c_p(addr(x)), c_p(addr(nrm)), c_p(addr(view)), c_p(addr(SD)), P, 1 if sphere else 0,
-                                                   pos_freq, ld_ol, refrac_freq, ld_rl, c_p(addr(dOL)), c_p(addr(dIL)), c_p(addr(dRL)),
-                                                   c_p(addr(dnov)), c_p(addr(dx)), c_p(addr(dn)), c_p(addr(dv)), c_p(addr(drho)),
-                                                   ctx.eng.stream()), "nu_s2_shade_encode_bwd")
+        ctx.eng.lib.nu_s2_shade_encode_bwd(addr(x), addr(nrm), addr(view), addr(SD), P, 1 if sphere else 0,
+                                           pos_freq, ld_ol, refrac_freq, ld_rl, addr(dOL), addr(dIL), addr(dRL),
+                                           addr(dnov), addr(dx), addr(dn), addr(dv), addr(drho), ctx.eng.stream())
         dm[:, 1] = drho
         return None, dx, dn, dv, dm, None, None, None, None, None
 
@@ -342,13 +323,11 @@ class _ShadeCombineFn(torch.autograd.Function):
         rc = torch.empty(P, device=dev)
         lib, S_ = eng.lib, eng.stream()
         if s2:
-            L.check(lib.nu_s2_shade_combine_fwd(c_p(addr(Mraw)), 8, c_p(addr(OLo)), c_p(addr(ILo)), c_p(addr(IWo)), c_p(addr(SD)),
-                                                c_p(addr(lut)), c_p(addr(idx)), P, ctypes.c_float(exp_max), 1 if internal else 0,
-                                                c_p(addr(color)), c_p(addr(rc)), S_), "nu_s2_shade_combine_fwd")
+            lib.nu_s2_shade_combine_fwd(addr(Mraw), 8, addr(OLo), addr(ILo), addr(IWo), addr(SD), addr(lut),
+                                        addr(idx), P, exp_max, 1 if internal else 0, addr(color), addr(rc), S_)
         else:
-            L.check(lib.nu_shade_combine_fwd(c_p(addr(Mraw)), 8, c_p(addr(OLo)), c_p(addr(ILo)), c_p(addr(IWo)), c_p(addr(RLo)),
-                                             c_p(addr(SD)), c_p(addr(lut)), c_p(addr(idx)), P, ctypes.c_float(exp_max), c_p(addr(color)),
-                                             c_p(0), S_), "nu_shade_combine_fwd")
+            lib.nu_shade_combine_fwd(addr(Mraw), 8, addr(OLo), addr(ILo), addr(IWo), addr(RLo),
+                                     addr(SD), addr(lut), addr(idx), P, exp_max, addr(color), None, S_)
         ctx.eng, ctx.cfg, ctx.bufs = eng, (exp_max, s2, internal), (Mraw, OLo, ILo, IWo, RLo, SD, idx, lut)
         ctx.set_materialize_grads(False)
         return color[:, :3].contiguous(), rc[:, None]
@@ -366,17 +345,14 @@ class _ShadeCombineFn(torch.autograd.Function):
         lib, S_ = eng.lib, eng.stream()
         if s2:
             g_rc = d_rc.reshape(P).contiguous() if d_rc is not None else None
-            L.check(lib.nu_s2_shade_combine_bwd(c_p(addr(Mraw)), 8, c_p(addr(OLo)), c_p(addr(ILo)), c_p(addr(IWo)), c_p(addr(SD)),
-                                                c_p(addr(lut)), c_p(addr(idx)), P, ctypes.c_float(exp_max), 1 if internal else 0,
-                                                c_p(addr(dc4)), c_p(addr(g_rc)), c_p(addr(dMraw)), c_p(addr(dOLo)), c_p(addr(dILo)),
-                                                c_p(addr(dIWo)), c_p(addr(dNoV)), S_), "nu_s2_shade_combine_bwd")
+            lib.nu_s2_shade_combine_bwd(addr(Mraw), 8, addr(OLo), addr(ILo), addr(IWo), addr(SD), addr(lut),
+                                        addr(idx), P, exp_max, 1 if internal else 0, addr(dc4), addr(g_rc),
+                                        addr(dMraw), addr(dOLo), addr(dILo), addr(dIWo), addr(dNoV), S_)
             dRL = None
         else:
             dRLo = torch.zeros_like(RLo)
-            L.check(lib.nu_shade_combine_bwd(c_p(addr(Mraw)), 8, c_p(addr(OLo)), c_p(addr(ILo)), c_p(addr(IWo)), c_p(addr(RLo)),
-                                             c_p(addr(SD)), c_p(addr(lut)), c_p(addr(idx)), P, ctypes.c_float(exp_max), c_p(addr(dc4)),
-                                             c_p(addr(dMraw)), c_p(addr(dOLo)), c_p(addr(dILo)), c_p(addr(dIWo)), c_p(addr(dRLo)),
-                                             c_p(addr(dNoV)), S_), "nu_shade_combine_bwd")
+            lib.nu_shade_combine_bwd(addr(Mraw), 8, addr(OLo), addr(ILo), addr(IWo), addr(RLo), addr(SD), addr(lut), addr(idx), P,
+                                     exp_max, addr(dc4), addr(dMraw), addr(dOLo), addr(dILo), addr(dIWo), addr(dRLo), addr(dNoV), S_)
             dRL = dRLo[:, :3]
         return None, dMraw[:, :6], dOLo[:, :3], dILo[:, :3], dIWo[:, None], dRL, dNoV[:, None], None, None, None, None
 
@@ -394,8 +370,7 @@ class _NeusAlphaFn(torch.autograd.Function):
         s1 = inv_s.detach().reshape(1).contiguous()
         P = sdf.shape[0]
         alpha = torch.empty(P, device=sdf.device)
-        L.check(eng.lib.nu_s2_neus_alpha_fwd(c_p(addr(sdf)), c_p(addr(nrm)), c_p(addr(dirs)), c_p(addr(dist)), c_p(addr(s1)),
-                                             ctypes.c_float(ca), P, c_p(addr(alpha)), eng.stream()), "nu_s2_neus_alpha_fwd")
+        eng.lib.nu_s2_neus_alpha_fwd(addr(sdf), addr(nrm), addr(dirs), addr(dist), addr(s1), ca, P, addr(alpha), eng.stream())
         ctx.eng, ctx.ca, ctx.s_shape = eng, ca, inv_s.shape
         ctx.save_for_backward(sdf, nrm, dirs, dist, s1)
         return alpha
@@ -406,9 +381,8 @@ class _NeusAlphaFn(torch.autograd.Function):
         P = sdf.shape[0]
         g_sdf, g_n, g_d, g_dist, g_s = torch.empty_like(sdf), torch.empty_like(nrm), torch.empty_like(dirs), torch.empty_like(dist), torch.empty_like(sdf)
         g_c = g.contiguous()
-        L.check(ctx.eng.lib.nu_s2_neus_alpha_bwd(c_p(addr(sdf)), c_p(addr(nrm)), c_p(addr(dirs)), c_p(addr(dist)), c_p(addr(s1)),
-                                                 ctypes.c_float(ctx.ca), P, c_p(addr(g_c)), c_p(addr(g_sdf)), c_p(addr(g_n)),
-                                                 c_p(addr(g_d)), c_p(addr(g_dist)), c_p(addr(g_s)), ctx.eng.stream()), "nu_s2_neus_alpha_bwd")
+        ctx.eng.lib.nu_s2_neus_alpha_bwd(addr(sdf), addr(nrm), addr(dirs), addr(dist), addr(s1), ctx.ca, P, addr(g_c),
+                                         addr(g_sdf), addr(g_n), addr(g_d), addr(g_dist), addr(g_s), ctx.eng.stream())
         return None, g_sdf, g_n, g_d, g_dist, g_s.sum().reshape(ctx.s_shape), None
 
 

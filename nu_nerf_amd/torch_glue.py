@@ -17,7 +17,7 @@ class _EmbedFn(torch.autograd.Function):
         x = x.detach().contiguous()
         P = x.shape[0]
         E = torch.empty(P, 64, device=x.device)
-        L.check(lib.nu_sdf_embed(L.ptr(x), 3, P, L.ptr(E), None, None, L.stream()), "nu_sdf_embed")
+        lib.nu_sdf_embed(L.ptr(x), 3, P, L.ptr(E), None, None, L.stream())
         ctx.E, ctx.nc = E, 3 + 6 * n_freq
         return E[:, :ctx.nc].clone()
 
@@ -30,7 +30,7 @@ class _EmbedFn(torch.autograd.Function):
         g = torch.zeros(P, 64, device=E.device)
         g[:, :ctx.nc] = dout
         dx = torch.empty(P, 3, device=E.device)
-        L.check(lib.nu_embed_jt(L.ptr(E), L.ptr(g), 64, None, 0, P, L.ptr(dx), L.stream()), "nu_embed_jt")
+        lib.nu_embed_jt(L.ptr(E), L.ptr(g), 64, None, 0, P, L.ptr(dx), L.stream())
         return dx, None
 
 
@@ -45,7 +45,7 @@ class _IdeFn(torch.autograd.Function):
         k = kappa_inv.detach().reshape(-1).contiguous()
         P = d.shape[0]
         out = torch.empty(P, 72, device=d.device)
-        L.check(lib.nu_ide(L.ptr(d), L.ptr(k), P, L.ptr(out), 72, L.stream()), "nu_ide")
+        lib.nu_ide(L.ptr(d), L.ptr(k), P, L.ptr(out), 72, L.stream())
         ctx.d, ctx.k, ctx.kshape = d, k, kappa_inv.shape
         return out
 
@@ -57,7 +57,7 @@ class _IdeFn(torch.autograd.Function):
         P = d.shape[0]
         g = g.contiguous()
         dd, dk = torch.empty(P, 3, device=d.device), torch.empty(P, device=d.device)
-        L.check(lib.nu_ide_bwd(L.ptr(d), L.ptr(k), L.ptr(g), 72, P, L.ptr(dd), L.ptr(dk), L.stream()), "nu_ide_bwd")
+        lib.nu_ide_bwd(L.ptr(d), L.ptr(k), L.ptr(g), 72, P, L.ptr(dd), L.ptr(dk), L.stream())
         return dd, dk.reshape(ctx.kshape)
 
 
@@ -70,7 +70,7 @@ class _EmbedNFn(torch.autograd.Function):
         x = x.detach().contiguous()
         P, nc = x.shape[0], 3 + 6 * n_freq
         out = torch.empty(P, nc, device=x.device)
-        L.check(L.load().nu_embed_n_fwd(L.ptr(x), P, n_freq, L.ptr(out), nc, L.stream()), "nu_embed_n_fwd")
+        L.load().nu_embed_n_fwd(L.ptr(x), P, n_freq, L.ptr(out), nc, L.stream())
         ctx.x, ctx.n_freq = x, n_freq
         return out
 
@@ -80,7 +80,7 @@ class _EmbedNFn(torch.autograd.Function):
         x = ctx.x
         g = dout.contiguous()
         dx = torch.empty_like(x)
-        L.check(L.load().nu_embed_n_bwd(L.ptr(x), L.ptr(g), g.shape[1], x.shape[0], ctx.n_freq, L.ptr(dx), L.stream()), "nu_embed_n_bwd")
+        L.load().nu_embed_n_bwd(L.ptr(x), L.ptr(g), g.shape[1], x.shape[0], ctx.n_freq, L.ptr(dx), L.stream())
         return dx, None
 
 

@@ -154,8 +154,7 @@ class FusedAdam(torch.optim.Optimizer):
                     d.p = p.data_ptr()        # (re-read every step: `module.to(...)` gives a Parameter new storage)
                 bk['count'] += 1
                 self._steps[bk['slots']] += 1
-                L.check(lib.nu_adam_step(descs, len(descs), ctypes.c_double(group['lr']), ctypes.c_double(b1),
-                                         ctypes.c_double(b2), ctypes.c_double(group['eps']), bk['count'], L.stream()), "nu_adam_step")
+                lib.nu_adam_step(descs, len(descs), group['lr'], b1, b2, group['eps'], bk['count'], L.stream())
             del keep
         return loss
 

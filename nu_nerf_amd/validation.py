@@ -16,14 +16,11 @@ from .shading_glue import shade
 
 def composite_weights(eng, ctx):
     """The per-sample composite weights of the last render_forward (the training path never materialises them)."""
-    from . import _lib as L
-    from .engine import c_p
     R, S = ctx['R'], ctx['S']
     w = eng.empty(R, S)
     rgb, acc, bg, ns = eng.empty(R, 3), eng.empty(R), eng.empty(R, 3), eng.empty(R)
-    L.check(eng.lib.nu_composite_fwd(c_p(addr(ctx['alpha_rm'])), c_p(addr(ctx['color_rm'])), c_p(addr(ctx['inner_rm'])), R, S,
-                                     c_p(addr(w)), c_p(addr(rgb)), c_p(addr(acc)), c_p(addr(bg)), c_p(addr(ns)), eng.stream()),
-            "nu_composite_fwd")
+    eng.lib.nu_composite_fwd(addr(ctx['alpha_rm']), addr(ctx['color_rm']), addr(ctx['inner_rm']),
+                             R, S, addr(w), addr(rgb), addr(acc), addr(bg), addr(ns), eng.stream())
     return w
 
 

@@ -57,12 +57,48 @@ def test_struct_layouts_match_python_mirrors(lib):
 
 
 def test_workspace_queries_are_pure_host_functions(lib):
-    lib.nu_wgrad_workspace_bytes.restype = ctypes.c_longlong
-    lib.nu_skinny_bwd_workspace_bytes.restype = ctypes.c_longlong
-    lib.nu_colsum_workspace_bytes.restype = ctypes.c_longlong
     assert lib.nu_wgrad_workspace_bytes(256, 256, 4, 1) == 4 * 256 * 257 * 4
     assert lib.nu_skinny_bwd_workspace_bytes(256, 3) > 0
     assert lib.nu_colsum_workspace_bytes(256) > 0
+
+
+def declared_parameter_counts():
+    """name -> parameter count of every nu_* declaration, NU_RM_ARGS (the remeshing entries' shared parameters) expanded."""
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "nu_nerf.h")).read(), flags=re.S).replace("\\\n", " ")
+    rm_args = re.search(r"#define NU_RM_ARGS (.*)", text).group(1)
+    text = re.sub(r"\bNU_RM_ARGS\b", rm_args, text)
+    return {name: 0 if params.strip() in ("", "void") else params.count(",") + 1
+            for name, params in re.findall(r"\b(nu_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)}
+
+
+def test_every_declared_function_is_bound_with_the_header_signature(lib):
+    counts = declared_parameter_counts()
+    assert sorted(counts) == declared_functions()
+    for name, n in counts.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == n, (name, fn.argtypes, n)
+        assert fn.restype in (ctypes.c_int, ctypes.c_longlong), name
+    assert lib.nu_mc_count.argtypes[4] is ctypes.c_float                        # float iso
+    assert lib.nu_adam_step.argtypes[2] is ctypes.c_double                       # double lr
+    assert lib.nu_wgrad_workspace_bytes.restype is ctypes.c_longlong
+    assert lib.nu_mc_count.argtypes[0] is ctypes.c_void_p and lib.nu_mc_count.argtypes[-1] is ctypes.c_void_p   # pointer, stream
+
+
+def test_long_long_results_keep_all_64_bits(lib):
+    nbytes = lib.nu_wgrad_workspace_bytes(1024, 1024, 1024, 1)
+    assert nbytes == 1024 * 1024 * 1025 * 4 and nbytes > 2 ** 31
+
+
+def test_negative_result_raises_naming_the_entry(lib):
+    """nu_gemm_nt rejects K % 32 != 0 before any HIP call: NU_ERR_ARG comes back, and the binding raises on it."""
+    from nu_nerf_amd._lib import NuNerfLibraryError
+    with pytest.raises(NuNerfLibraryError, match=r"nu_gemm_nt failed with code -1"):
+        lib.nu_gemm_nt(None, 32, None, 32, 64, 64, 3, None, 64, None, 0, None, None, 0, None, 0, None, 0, 0, 1.0, 0, None)
+
+
+def test_missing_argument_is_a_type_error_before_the_call(lib):
+    with pytest.raises(TypeError):
+        lib.nu_wgrad_workspace_bytes(1024, 1024, 1024)
 
 
 def test_code_object_targets_gfx950_only():

@@ -91,7 +91,6 @@ def test_nt_derivative_epilogues(gpu):
 def test_tn_weight_grad(gpu, P, N1, N2, S):
     from nu_nerf_amd import _lib as L
     lib = L.load()
-    lib.nu_gemm_tn_workspace_bytes.restype = ctypes.c_longlong
     torch.manual_seed(P)
     lda, ldb = (N1 + 3) // 4 * 4 + 4, (N2 + 3) // 4 * 4
     A0 = torch.randn(P, lda, device=gpu)
@@ -115,7 +114,6 @@ def test_tn_weight_grad_operand_over_4gib(gpu):
     """Operands of 4 GiB or more take the 64-bit-offset build of the TN kernel (32-bit byte offsets elsewhere)."""
     from nu_nerf_amd import _lib as L
     lib = L.load()
-    lib.nu_gemm_tn_workspace_bytes.restype = ctypes.c_longlong
     P, ld, N1, N2, S = (1 << 20) + 77, 1024, 96, 130, 64
     X = torch.empty(P, ld, device=gpu)
     X.normal_()
@@ -357,7 +355,6 @@ def test_bf16_tn_weight_grad(gpu, P, N1, N2, S):
     from nu_nerf_amd import _lib as L
     from nu_nerf_amd.engine import GemmTN, addr
     lib = L.load()
-    lib.nu_wgrad_workspace_bytes.restype = ctypes.c_longlong
     torch.manual_seed(P)
     lda, ldb = (N1 + 3) // 4 * 4 + 4, (N2 + 3) // 4 * 4
     A0, B0 = torch.randn(P, lda, device=gpu), torch.randn(P, ldb, device=gpu)
@@ -468,7 +465,6 @@ def test_bf16_storage_tn_weight_grad(gpu, P, N1, N2, S, flags):
     from nu_nerf_amd import _lib as L
     from nu_nerf_amd.engine import GemmTN, addr
     lib = L.load()
-    lib.nu_wgrad_workspace_bytes.restype = ctypes.c_longlong
     torch.manual_seed(P)
     lda, ldb = (N1 + 7) // 8 * 8 + 8, (N2 + 7) // 8 * 8
     ops = [torch.randn(P, ld, device=gpu) for ld in (lda, ldb, lda, ldb)]
@@ -625,7 +621,6 @@ def test_bf16x6_tn_is_fp32_equivalent(gpu, P, N1, N2, S):
     from nu_nerf_amd import _lib as L
     from nu_nerf_amd.engine import GemmTN, addr
     lib = L.load()
-    lib.nu_wgrad_workspace_bytes.restype = ctypes.c_longlong
     torch.manual_seed(P)
     lda, ldb = (N1 + 3) // 4 * 4 + 4, (N2 + 3) // 4 * 4
     A0, B0 = torch.randn(P, lda, device=gpu), torch.randn(P, ldb, device=gpu) * torch.exp(2 * torch.randn(P, 1, device=gpu))
@@ -671,7 +666,6 @@ def test_bf16_storage_skinny_heads(gpu, P, K, NO):
     from nu_nerf_amd import _lib as L
     from nu_nerf_amd.engine import ReduceDesc, addr
     lib = L.load()
-    lib.nu_skinny_bwd_workspace_bytes.restype = ctypes.c_longlong
     torch.manual_seed(P + K)
     H = torch.relu(torch.randn(P, K, device=gpu)).bfloat16()
     W = torch.randn(NO, K, device=gpu) / K ** 0.5

@@ -14,7 +14,6 @@ pytestmark = pytest.mark.gpu
 def test_skinny_bwd(gpu, P, K, NO, ldy, relu_mask, accumulate):
     from nu_nerf_amd import _lib as L
     lib = L.load()
-    lib.nu_skinny_bwd_workspace_bytes.restype = ctypes.c_longlong
     torch.manual_seed(P + K + NO)
     ldh = K + 32
     H = torch.randn(P, ldh, device=gpu)
