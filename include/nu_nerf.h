@@ -324,6 +324,28 @@ int nu_brute_closest(const float* V, const int* F, int n_faces, const float* pts
                      float* closest, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Stage-2 object masks of real captures: render_mask.py -> utils/render_mask_real.py (one OptiX trace per pixel of every training
+ * image against the stage-1 mesh) and mask_erosion.py (cv.erode with a k x k box, composed with the inverted original).
+ *   cams [n_img, 21] per image: Kinv [3x3] then the world -> camera [R|t] [3x4], both row-major.  Pixel (x, y) of image i:
+ *   c = (x + 0.5, y + 0.5, 1), d = normalize(R^T (Kinv c)), o = -R^T t; tmin = 0, tmax = 1e16 (cuda/triangle.cu).
+ *   out [n_img, h, w] uint8 = 255 where the pixel's ray hits a triangle, 0 elsewhere: any-hit traversal of the tree of
+ *   nu_lbvh_build, the ray made in registers (no ray buffer); the same predicate as nu_lbvh_trace's hit flag, bit for bit.
+ *   n_img * ceil(h / 4) * ceil(w / 4) must stay below 2^31 (chunk over images).
+ * --------------------------------------------------------------------------------------------------------- */
+int nu_mask_pinhole_trace(const void* bvh, int n_faces, const float* cams, int n_img, int h, int w, unsigned char* out,
+                          hipStream_t stream);
+/* the same rays as rays [n_img * h * w, 6] = (origin, direction), pixel-major per image (tests; not on the hot path) */
+int nu_mask_pinhole_rays(const float* cams, int n_img, int h, int w, float* rays, hipStream_t stream);
+/* m, out [n, h, w] uint8, k >= 1 (anything else: NU_ERR_ARG), anchor a = k / 2:
+ *   eroded[y, x] = min m[y + dy, x + dx], dy, dx in [-a, k - 1 - a], positions outside the image left out (OpenCV's default
+ *                  constant border of 255 for erosion);
+ *   out          = eroded + (max(m) - m), max over each image (computed on the device).
+ * `work` is a caller-owned buffer of nu_mask_erode_workspace_bytes(n, h, w) bytes; out must not alias m. */
+long long nu_mask_erode_workspace_bytes(int n, int h, int w);
+int nu_mask_erode(const unsigned char* m, int n, int h, int w, int k, void* work, long long work_bytes, unsigned char* out,
+                  hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Network-level entry points: one call sequences every kernel launch of a network pass from C++.
  *   nu_sdf_mlp_{fwd,normal,bwd}      SDFNetwork.forward / .gradient and their (double) backward   field.py:133-170
  *   nu_nerfpp_mlp_{fwd,bwd}          NeRFNetwork.forward / backward                               field.py:265-289

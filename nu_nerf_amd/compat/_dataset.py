@@ -4,14 +4,18 @@ import numpy as np
 import torch
 
 
-def build_imgs_info(database, img_ids, is_nerf=False):
+def build_imgs_info(database, img_ids, is_nerf=False, s2_mask=False):
     """What the reference's module-level build_imgs_info returns (renderer_zerothick.py:20-45), from the database interface of
     dataset/database.py (`get_image` uint8 [h,w,3], `get_pose` [3,4], `get_K` [3,3], `get_depth` -> (depth, mask)): colours
-    scaled to [0,1] (utils/base_utils.py color_map_forward), stacked over the images; masks for the NeRF-synthetic databases."""
+    scaled to [0,1] (utils/base_utils.py color_map_forward), stacked over the images; masks for the NeRF-synthetic databases.
+    s2_mask (the non-zero-thickness stage 2 with cfg get_mask, renderer.py:22-55): also 'mask' = the stacked
+    `database.get_mask(i)` (the eroded mask_erosion/ image / 255, [h,w,1]) as float32."""
     imgs = np.stack([database.get_image(i) for i in img_ids], 0).astype(np.float32) / 255.0
     info = {'imgs': imgs,
             'Ks': np.stack([database.get_K(i) for i in img_ids], 0).astype(np.float32),
             'poses': np.stack([database.get_pose(i) for i in img_ids], 0).astype(np.float32)}
+    if s2_mask:
+        info['mask'] = np.stack([database.get_mask(i) for i in img_ids], 0).astype(np.float32)
     if is_nerf:
         info['masks'] = np.stack([database.get_depth(i)[1] for i in img_ids], 0)
     return info
@@ -43,8 +47,9 @@ class ReferenceDatasetMixin:
         self.database = parse_database_name(name, self.cfg.get('dataset_dir'))
         train_ids, test_ids = get_database_split(self.database)
         self.train_ids, self.test_ids = np.asarray(train_ids), test_ids
-        train = imgs_info_to_torch(build_imgs_info(self.database, self.train_ids, self.is_nerf))
-        test = imgs_info_to_torch(build_imgs_info(self.database, self.test_ids, self.is_nerf))
+        s2_mask = self.cfg.get('get_mask', False)
+        train = imgs_info_to_torch(build_imgs_info(self.database, self.train_ids, self.is_nerf, s2_mask))
+        test = imgs_info_to_torch(build_imgs_info(self.database, self.test_ids, self.is_nerf, s2_mask))
         _, _, h, w = train['imgs'].shape
         print(f'training size {h} {w} ...')
         # built on the CPU like the reference's (the parameters are not on the GPU yet: the trainer calls .cuda() on the finished

@@ -376,20 +376,82 @@ template <int CTRL> static __device__ __forceinline__ float nu_quad_f(float v) {
 #define NU_QP_XOR1 0xB1         // quad_perm:[1,0,3,2]
 #define NU_QP_XOR2 0x4E         // quad_perm:[2,3,0,1]
 #define NU_QP_XOR3 0x1B         // quad_perm:[3,2,1,0]
-__global__ __launch_bounds__(64) void lbvh_trace_quad_kernel(const char* __restrict__ buf, NuBvhLayout L, const float* __restrict__ rays,
-                                                             int N, float tmin, float tmax, float* __restrict__ hit,
-                                                             int* __restrict__ idx, float* __restrict__ tout) {
+
+// Ray sources of the traversal kernel.  begin() fetches (or computes) the ray of quad q of block blk and returns false when the quad
+// has no ray; end() stores the verdict.  Every lane of a quad calls begin(); only lane 0 of the quad calls end().
+struct NuRayBuffer {                       // rays [N,6] from memory -> (hit, idx, t) per ray: nu_lbvh_trace
+    const float* __restrict__ rays;
+    int N;
+    float* __restrict__ hit;
+    int* __restrict__ idx;
+    float* __restrict__ tout;
+    int r;
+    __device__ __forceinline__ bool begin(int blk, int q, float* o, float* d) {
+        r = blk * 16 + q;
+        if (r >= N) return false;
+        for (int k = 0; k < 3; ++k) { o[k] = rays[r * 6LL + k]; d[k] = rays[r * 6LL + 3 + k]; }
+        return true;
+    }
+    __device__ __forceinline__ void end(int found, int best_id, float best_t) {
+        hit[r] = found ? 1.0f : 0.0f;
+        idx[r] = best_id;
+        if (tout) tout[r] = found ? best_t : 0.0f;
+    }
+};
+
+// The camera ray of pixel (x, y) in the real-capture convention (utils/render_mask_real.py:52-67, the ray store of
+// renderer._construct_ray_batch): c = (x + 0.5, y + 0.5, 1), d = normalize(R^T (Kinv c)), o = -R^T t.  cam = Kinv [3x3] then the
+// world -> camera [R|t] [3x4], both row-major.  Single-rounding fp32 operations in a fixed order (contraction is off in this file): the
+// one definition nu_mask_pinhole_rays and nu_mask_pinhole_trace share, so the two are bit-identical.
+#define NU_CAM_FLOATS 21
+static __device__ inline void nu_pinhole_ray(const float* __restrict__ cam, int x, int y, float* o, float* d) {
+    const float* Ki = cam;
+    const float* P = cam + 9;
+    const float c0 = (float)x + 0.5f, c1 = (float)y + 0.5f;
+    float kc[3];
+    for (int i = 0; i < 3; ++i) kc[i] = (Ki[i * 3] * c0 + Ki[i * 3 + 1] * c1) + Ki[i * 3 + 2];
+    float v[3];
+    for (int j = 0; j < 3; ++j) {
+        v[j] = (P[j] * kc[0] + P[4 + j] * kc[1]) + P[8 + j] * kc[2];                       // (R^T kc)_j
+        o[j] = -((P[j] * P[3] + P[4 + j] * P[7]) + P[8 + j] * P[11]);                      // -(R^T t)_j
+    }
+    const float n = sqrtf((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    for (int j = 0; j < 3; ++j) d[j] = v[j] / n;
+}
+
+struct NuPinholeMask {                     // every pixel of n images -> uint8 0 / 255 per pixel: nu_mask_pinhole_trace
+    const float* __restrict__ cams;        // [n, NU_CAM_FLOATS]
+    int h, w, tiles_x, tiles;              // 4 x 4 pixel tiles per image, one tile per 16-ray wave
+    unsigned char* __restrict__ out;       // [n, h, w]
+    long long p;
+    __device__ __forceinline__ bool begin(int blk, int q, float* o, float* d) {
+        const int img = blk / tiles, t = blk - img * tiles;
+        const int ty = t / tiles_x, tx = t - ty * tiles_x;
+        const int x = tx * 4 + (q & 3), y = ty * 4 + (q >> 2);
+        if (x >= w || y >= h) return false;
+        p = ((long long)img * h + y) * w + x;
+        nu_pinhole_ray(cams + (long long)img * NU_CAM_FLOATS, x, y, o, d);
+        return true;
+    }
+    __device__ __forceinline__ void end(int found, int, float) { out[p] = found ? 255 : 0; }
+};
+
+// ANY_HIT = false: closest hit (nu_lbvh_trace).  ANY_HIT = true: the ray ends as soon as a lane of its quad accepts a triangle; until
+// then the running best is tmax, so the walk is step for step the closest-hit walk and `found` is the same predicate (the boxes are
+// padded so that no accepted triangle is ever culled) -- only the (t, face id) of an any-hit are not the closest ones.
+template <class RaySrc, bool ANY_HIT>
+__global__ __launch_bounds__(64) void lbvh_trace_quad_kernel(const char* __restrict__ buf, NuBvhLayout L, RaySrc src, float tmin,
+                                                             float tmax) {
     __shared__ int stack[NU_WSTACK][16];
     const int lane = threadIdx.x & 63, sub = lane & 3, q = lane >> 2;
-    const int r = blockIdx.x * 16 + q;
-    if (r >= N) return;                                    // whole quads leave together
+    float o[3], d[3], invd[3];
+    if (!src.begin(blockIdx.x, q, o, d)) return;           // whole quads leave together
     const NuBvhHeader* h = (const NuBvhHeader*)(buf + L.header);
     const NuBvhWideEntry* wide = (const NuBvhWideEntry*)(buf + L.wide);
     const float* tris = (const float*)(buf + L.tris);
     const int* ids = (const int*)(buf + L.ids);
     const int n = h->n_faces;
-    float o[3], d[3], invd[3];
-    for (int k = 0; k < 3; ++k) { o[k] = rays[r * 6LL + k]; d[k] = rays[r * 6LL + 3 + k]; invd[k] = 1.0f / d[k]; }
+    for (int k = 0; k < 3; ++k) invd[k] = 1.0f / d[k];
     float best_t = tmax;
     int best_id = NU_MISS_INDEX;
     int found = 0;
@@ -430,7 +492,7 @@ __global__ __launch_bounds__(64) void lbvh_trace_quad_kernel(const char* __restr
 #endif
             float tn;
             // inclusive in best_t: an equal-t hit with a lower face id must still be found
-            const bool hb = e.ref != NU_WIDE_EMPTY && nu_ray_box(o, invd, e.bmin, e.bmax, tmin, best_t, tn);
+            const bool hb = e.ref != NU_WIDE_EMPTY && nu_ray_box(o, invd, e.bmin, e.bmax, tmin, ANY_HIT ? tmax : best_t, tn);
             const bool leaf = hb && e.ref < 0;
             const int pos = leaf ? -1 - e.ref : 0;
             float tv[9];
@@ -479,18 +541,14 @@ __global__ __launch_bounds__(64) void lbvh_trace_quad_kernel(const char* __restr
                 if (nu_ray_tri(o, d, tv, tv + 3, tv + 6, tmin, tmax, t)) { cf = 1; ct = t; ci = tid; }
             }
             merge(cf, ct, ci);
-            if (done) break;
+            if (done || (ANY_HIT && found)) break;
             e = e2;
         }
 #ifdef NU_LBVH_STATS
         best_t = (float)steps; found = 1;                  // development build: t_out reports the number of records visited
 #endif
     }
-    if (sub == 0) {
-        hit[r] = found ? 1.0f : 0.0f;
-        idx[r] = best_id;
-        if (tout) tout[r] = found ? best_t : 0.0f;
-    }
+    if (sub == 0) src.end(found, best_id, best_t);
 }
 
 extern "C" int nu_lbvh_trace(const void* bvh, int n_faces, const float* rays, int N, float tmin, float tmax, float* hit,
@@ -499,8 +557,47 @@ extern "C" int nu_lbvh_trace(const void* bvh, int n_faces, const float* rays, in
     const NuBvhLayout L = nu_bvh_layout(n_faces);
     // four lanes per ray at every batch size: against the one-lane-per-ray kernel (since removed) 4 096 rays took 75 -> 39 us
     // object-aimed, 49 -> 32 us camera rays; 2^20 rays 1.82 -> 2.67 and 4.22 -> 4.96 G rays/s (profiles/r03/lbvh_bench.txt)
-    hipLaunchKernelGGL(lbvh_trace_quad_kernel, dim3(nu_cdiv(N, 16)), dim3(64), 0, stream, (const char*)bvh, L, rays, N, tmin, tmax,
-                       hit, idx, t_out);
+    const NuRayBuffer src = {rays, N, hit, idx, t_out, 0};
+    hipLaunchKernelGGL((lbvh_trace_quad_kernel<NuRayBuffer, false>), dim3(nu_cdiv(N, 16)), dim3(64), 0, stream, (const char*)bvh, L, src,
+                       tmin, tmax);
+    return nu_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------
+// object masks of real captures (utils/render_mask_real.py): one any-hit trace per pixel, rays made in registers
+// ------------------------------------------------------------------------------------------------
+extern "C" int nu_mask_pinhole_trace(const void* bvh, int n_faces, const float* cams, int n_img, int h, int w, unsigned char* out,
+                                     hipStream_t stream) {
+    if (n_img < 0 || h <= 0 || w <= 0 || n_faces <= 0 || !bvh || !cams || !out) return NU_ERR_ARG;
+    if (n_img == 0) return NU_OK;
+    const int tiles_x = nu_cdiv(w, 4), tiles_y = nu_cdiv(h, 4);
+    const long long blocks = (long long)n_img * tiles_x * tiles_y;
+    if (blocks > 0x7fffffffLL) return NU_ERR_ARG;         // the caller chunks over images
+    const NuBvhLayout L = nu_bvh_layout(n_faces);
+    const NuPinholeMask src = {cams, h, w, tiles_x, tiles_x * tiles_y, out, 0};
+    // tmin = 0, tmax = 1e16: the raygen program of cuda/triangle.cu
+    hipLaunchKernelGGL((lbvh_trace_quad_kernel<NuPinholeMask, true>), dim3((unsigned)blocks), dim3(64), 0, stream, (const char*)bvh, L,
+                       src, 0.0f, 1e16f);
+    return nu_launch_status();
+}
+
+__global__ __launch_bounds__(256) void mask_pinhole_rays_kernel(const float* __restrict__ cams, int n_img, int h, int w,
+                                                                float* __restrict__ rays) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long hw = (long long)h * w;
+    if (p >= hw * n_img) return;
+    const int img = (int)(p / hw);
+    const int rem = (int)(p - img * hw), y = rem / w, x = rem - y * w;
+    float o[3], d[3];
+    nu_pinhole_ray(cams + (long long)img * NU_CAM_FLOATS, x, y, o, d);
+    for (int k = 0; k < 3; ++k) { rays[p * 6 + k] = o[k]; rays[p * 6 + 3 + k] = d[k]; }
+}
+extern "C" int nu_mask_pinhole_rays(const float* cams, int n_img, int h, int w, float* rays, hipStream_t stream) {
+    if (n_img < 0 || h <= 0 || w <= 0 || !cams || !rays) return NU_ERR_ARG;
+    const long long N = (long long)n_img * h * w;
+    if (N == 0) return NU_OK;
+    if (nu_cdivl(N, 256) > 0x7fffffffLL) return NU_ERR_ARG;
+    hipLaunchKernelGGL(mask_pinhole_rays_kernel, dim3((unsigned)nu_cdivl(N, 256)), dim3(256), 0, stream, cams, n_img, h, w, rays);
     return nu_launch_status();
 }
 

@@ -510,7 +510,10 @@ class Stage2Renderer(nn.Module):
             poses, idxs = self.train_poses, batch['idxs'][..., 0]
             rays_o = (poses[:, :, :3].permute(0, 2, 1) @ -poses[:, :, 3:])[idxs, :, 0]
             rays_d = (poses[idxs, :, :3].permute(0, 2, 1) @ batch['dirs'].unsqueeze(-1))[..., 0]
-            batch = {'rays_o': rays_o, 'rays_d': rays_d, 'rgbs': batch['rgbs']}
+            rays = {'rays_o': rays_o, 'rays_d': rays_d, 'rgbs': batch['rgbs']}
+            if 'mask' in batch:     # per-ray weight of the non-zero-thickness model's get_mask store (stage2_thick.py)
+                rays['masks'] = batch['mask']
+            batch = rays
         return self.train_step_rays(batch, step)
 
     _EVAL_KEYS = ('ray_rgb', 'gradient_error', 'normal', 'tir_mask', 'specular_light', 'specular_color', 'specular_ref')
@@ -528,6 +531,8 @@ class Stage2Renderer(nn.Module):
                 outs[k].append(o[k].detach())
         outs = {k: torch.cat(v, 0) for k, v in outs.items()}
         tm = outs['tir_mask'].float()
+        if 'mask' in batch:         # the test image's eroded mask (stage2_thick.py, get_mask; renderer.py:1301-1305)
+            tm = tm * batch['mask'].reshape(-1, 1)
         if 'rgbs' in batch:
             outs['loss_rgb'] = self.compute_rgb_loss(outs['ray_rgb'] * tm, batch['rgbs'] * tm)
         return outs
@@ -549,6 +554,8 @@ class Stage2Renderer(nn.Module):
         with torch.no_grad():
             outputs = self.render_eval(batch, step)
         tm = outputs['tir_mask'].float()
+        if 'mask' in batch:
+            tm = tm * batch['mask'].reshape(-1, 1)
         outputs['gt_rgb'] = (batch['rgbs'] * tm).reshape(h, w, 3)
         outputs['ray_rgb'] = (outputs['ray_rgb'] * tm).reshape(h, w, 3)
         outputs['gt_depth'] = depth

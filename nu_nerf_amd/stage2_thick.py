@@ -68,6 +68,37 @@ class Stage2Renderer(_ZeroThickStage2):
         if training:
             self._init_dataset()
 
+    # ---- get_mask: the eroded object mask as a per-ray weight (renderer.py:1062-1084, :1303-1305, :1326-1330) ---------------------
+    def _uses_mask(self, imgs_info):
+        return bool(self.get_mask) and not self.is_nerf and imgs_info is not None and 'mask' in imgs_info
+
+    @staticmethod
+    def _ray_mask(mask, h, w):
+        """imgs_info['mask'] [n,H,W,1] or [n,H,W] (build_imgs_info(s2_mask=True), mask_render.stage2_masks) -> float [n*h*w, 1],
+        pixel-major per image like the store's rgbs; resized nearest when the images were down-sampled (as imgs_info_downsample
+        resizes 'masks'; the reference never resizes 'mask' and fails on the size mismatch)."""
+        n = mask.shape[0]
+        m = mask.reshape(n, 1, mask.shape[1], mask.shape[2]).float()
+        if tuple(m.shape[2:]) != (h, w):
+            m = torch.nn.functional.interpolate(m, size=(h, w), mode='nearest')
+        return m.reshape(n * h * w, 1)
+
+    def _construct_ray_batch(self, imgs_info, device=None):
+        """renderer._construct_ray_batch plus, with cfg get_mask and a 'mask' in imgs_info, the per-ray 'mask' aligned with
+        'rgbs' / 'idxs' (renderer.py:1062-1084): shuffled and sliced with them, handed to train_step_rays as batch['masks']."""
+        batch, poses, rn, h, w = NeROShapeRenderer._construct_ray_batch(imgs_info, device)
+        if self._uses_mask(imgs_info):
+            batch['mask'] = self._ray_mask(imgs_info['mask'].to(batch['rgbs'].device), h, w)
+        return batch, poses, rn, h, w
+
+    def _test_batch_from_store(self, index, dev):
+        """The test image's rays as stage2.py's, plus its mask as batch['mask'] under get_mask: test_step and render_eval multiply
+        ray_rgb / gt_rgb (and the loss) by it (renderer.py:1301-1305)."""
+        batch, h, w, depth, mask = NeROShapeRenderer._test_batch_from_store(self, index, dev)
+        if self._uses_mask(self.test_imgs_info):
+            batch['mask'] = self._ray_mask(self.test_imgs_info['mask'][index:index + 1].to(dev), h, w)
+        return batch, h, w, depth, mask
+
     def _init_own_parameters(self):
         from .params import init_stage2_thick_own_params
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
