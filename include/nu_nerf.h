@@ -346,6 +346,30 @@ int nu_mask_erode(const unsigned char* m, int n, int h, int w, int k, void* work
                   hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Validation metrics (network/metrics.py): PSNR and SSIM of uint8 images [n, h, w, c], channel-interleaved, c in {1, 3}.
+ * Pointers need no alignment.  DESIGN.md section 18 has the exactness argument and the reduction order.
+ * --------------------------------------------------------------------------------------------------------- */
+/* color_map_backward (utils/base_utils.py:501-504): out = (uint8) clamp(x * 255, 0, 255) -- one fp32 multiply, truncation toward
+ * zero; equal to numpy byte for byte on every finite input and on +-inf.  NaN gives 0 (numpy's cast of NaN is undefined). */
+int nu_img_quantize(const float* x, long long count, unsigned char* out, hipStream_t stream);
+/* ssd[i] = sum over the per_image bytes of image i of (a - b)^2, as an exact 64-bit integer (ssd is zeroed inside; integer
+ * atomics, so the result does not depend on the order). */
+int nu_img_sqdiff(const unsigned char* a, const unsigned char* b, int n, long long per_image, long long* ssd, hipStream_t stream);
+/* skimage.metrics.structural_similarity(a[i], b[i], win_size=win, channel_axis=2, data_range=255): uniform win x win window,
+ * sample covariance, C1 = (0.01 * 255)^2, C2 = (0.03 * 255)^2,
+ *   S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2))
+ * on the (h - win + 1)(w - win + 1) windows that lie inside the image (skimage's crop), per channel.
+ *   mssim [n]                                   the mean of S over windows and channels
+ *   smap  [n, h - win + 1, w - win + 1, c]      S itself; NULL: not written
+ * Window sums are exact integers, S is fp64, the mean is reduced in a fixed order: the same bits on every run, and for an image
+ * whatever the batch it is in.  win must be odd, 3 <= win <= 15, win <= h, win <= w (anything else: NU_ERR_ARG; skimage raises).
+ * `work` is a caller-owned buffer of nu_img_ssim_workspace_bytes(n, h, w, c) bytes (enough for every win).  n * ceil((h - win + 1)
+ * / 16) * ceil((w - win + 1) c / 64) must stay below 2^31 (chunk over images). */
+long long nu_img_ssim_workspace_bytes(int n, int h, int w, int c);
+int nu_img_ssim(const unsigned char* a, const unsigned char* b, int n, int h, int w, int c, int win, double* mssim, double* smap,
+                void* work, long long work_bytes, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Network-level entry points: one call sequences every kernel launch of a network pass from C++.
  *   nu_sdf_mlp_{fwd,normal,bwd}      SDFNetwork.forward / .gradient and their (double) backward   field.py:133-170
  *   nu_nerfpp_mlp_{fwd,bwd}          NeRFNetwork.forward / backward                               field.py:265-289
