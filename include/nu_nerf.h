@@ -502,6 +502,27 @@ int nu_shading_stack_fwd(NuOpCtx* ctx, const NuShadeNet* net, NuShadeBufs* bufs,
 int nu_shading_stack_bwd(NuOpCtx* ctx, const NuShadeNet* net, NuShadeBufs* bufs, const float* YX, const float* nrm, const float* pt,
                          const int* idx, const float* dcolor_rm, int stage, hipStream_t stream);
 
+/* Per-vertex material baking (predict_materials, network/renderer_zerothick.py:846-864; the arrays relight_backend.py:26-28 reads)
+ * as ONE fully-fused no-gradient kernel (csrc/bake.hip): x -> embedding -> SDF network -> [sdf | feature | x] kept in LDS -> the
+ * material predictors (288 -> 256 -> 256 -> 256 ReLU -> head) -> sigmoid.  Exact fp32 in the k order of the layered path
+ * (nu_sdf_mlp_fwd(..., want_feat = 1) + the materials part of nu_shading_stack_fwd): sdf, feature columns and raw heads are
+ * bit-identical to it.  NuBakeNet: the SDF network's layers plus the packed material tables as NuShadeNet holds them (4 predictors
+ * side by side: metallic, roughness, albedo, transmission weight; n_pred = 3 for a network without the last).
+ *   X [P, x_ld] (x = the first three floats of a row, x_ld >= 3); metallic, roughness [P]; albedo [P,3]; transmission, sdf [P].
+ *   Every output pointer may be NULL; a predictor whose output is NULL is not evaluated.  P <= 0 returns at once.
+ *   Debug / test fields: feat != NULL also writes the feature columns [P,256]; raw != 0 writes the heads before the sigmoid. */
+typedef struct NuBakeNet {
+    NuSdfNet sdf;
+    const float *WpM0, *bM0;                        /* [256 n_pred, 288], [256 n_pred] */
+    const float* WpM[3]; const float* bM[3];        /* [1], [2]: [n_pred, 256, 256], [n_pred, 256] */
+    const float *Ws6, *b6;                          /* block-diagonal heads [6, 1024], [6] */
+    float* feat;
+    int n_pred, raw;
+} NuBakeNet;
+int nu_bake_net_size(void);
+int nu_material_bake_fwd(const NuBakeNet* net, const float* X, int x_ld, int P, float* metallic, float* roughness, float* albedo,
+                         float* transmission, float* sdf, hipStream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * Fused loss assembly: from the renderer's per-ray outputs to the scalar the trainer back-propagates, for
  * the loss set of the shipped stage-1 configs -- white background + clamp (renderer_zerothick.py:783-787), charbonier RGB

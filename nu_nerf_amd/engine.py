@@ -109,6 +109,12 @@ class ShadeNet(ctypes.Structure):
                 ("WpM0_16", c_p), ("WpTM0_16", c_p), ("WpM16", c_p * 3), ("WpTM16", c_p * 3)]
 
 
+class BakeNet(ctypes.Structure):
+    """Mirror of NuBakeNet: the SDF network plus the packed material tables, and the debug outputs of the bake kernel."""
+    _fields_ = [("sdf", SdfNet), ("WpM0", c_p), ("bM0", c_p), ("WpM", c_p * 3), ("bM", c_p * 3), ("Ws6", c_p), ("b6", c_p),
+                ("feat", c_p), ("n_pred", c_int), ("raw", c_int)]
+
+
 class ShadeBufs(ctypes.Structure):
     _fields_ = [("P", c_int), ("R", c_int), ("extra_dirs", c_p), ("extra_pts", c_p), ("M", c_p * 3), ("maskM", c_p * 3), ("Mraw", c_p),
                 ("OLin", c_p), ("ILin", c_p), ("IWin", c_p), ("RLin", c_p), ("SD", c_p),
@@ -194,7 +200,8 @@ class Stage1Engine:
         self._wg_depth, self._wg_held = 0, []
         self._ndesc_p = ctypes.cast(ctypes.addressof(self._ctx) + OpCtx.ndesc.offset, ctypes.POINTER(c_int))
         for fn, st in (("nu_op_ctx_size", OpCtx), ("nu_sdf_net_size", SdfNet), ("nu_sdf_bufs_size", SdfBufs), ("nu_nerf_net_size", NerfNet),
-                       ("nu_nerf_bufs_size", NerfBufs), ("nu_shade_net_size", ShadeNet), ("nu_shade_bufs_size", ShadeBufs)):
+                       ("nu_nerf_bufs_size", NerfBufs), ("nu_shade_net_size", ShadeNet), ("nu_shade_bufs_size", ShadeBufs),
+                       ("nu_bake_net_size", BakeNet)):
             assert getattr(lib, fn)() == ctypes.sizeof(st), f"{st.__name__} ABI mismatch"
         # NU_PY_SEQ=1: sequence every launch from Python (the path bench.py's per-launch event timing uses)
         self.py_seq = os.environ.get('NU_PY_SEQ', '0') != '0'
@@ -828,6 +835,21 @@ class Stage1Engine:
             self._forced_flush()
         ws, nb = self._arena_take(self.lib.nu_colsum_workspace_bytes(ncols))
         self.lib.nu_colsum_enqueue(A, lda, P, ncols, out, accumulate, ws, nb, self._rd, self._ndesc_p, self._rd_cap, self.stream())
+
+    # ------------------------------------------------------------------ material bake
+    def material_bake(self, X, x_ld, P, metallic=None, roughness=None, albedo=None, transmission=None, sdf=None, feat=None, raw=False):
+        """Materials of P points (X: device address of [P, x_ld] rows whose first 3 floats are x) in ONE kernel (csrc/bake.hip): sigmoid of
+        the material predictors on [SDF feature | x], written to the fp32 tensors given (metallic, roughness, transmission, sdf [P];
+        albedo [P,3]; None: not evaluated).  Reads the fp32 packed tables, which pack() writes in every mlp_dtype: the bake is fp32 also on
+        a bf16-storage or bf16x6 engine.  feat [P,256] / raw: the kernel's test outputs (feature columns; heads before the sigmoid)."""
+        if self._desc_dev is None or self._ptr_sig != self._signature():
+            self._upload_descs()
+        n = BakeNet(sdf=self._sdf_net, WpM0=addr(self.WpM0), bM0=addr(self.bM0), Ws6=addr(self.Ws6), b6=addr(self.b6),
+                    feat=addr(feat), n_pred=4, raw=1 if raw else 0)
+        for j in (1, 2):
+            n.WpM[j], n.bM[j] = addr(self.WpM[j]), addr(self.bM[j])
+        self.lib.nu_material_bake_fwd(ctypes.byref(n), X, x_ld, P, addr(metallic), addr(roughness), addr(albedo), addr(transmission),
+                                      addr(sdf), self.stream())
 
     # ------------------------------------------------------------------ SDF network
     def sdf_forward(self, X, x_ld, P, *, keep=True, want_feat=True):

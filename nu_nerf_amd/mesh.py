@@ -187,8 +187,10 @@ def stage2_inner_grid(stage2_renderer, resolution, slab_points=None):
     return torch.where(s1 < 0, inner, torch.ones_like(inner))
 
 
-def write_ply(path, V, F):
-    """Binary little-endian PLY: float x, y, z per vertex; uchar count + int vertex indices per face."""
+def write_ply(path, V, F, colors=None):
+    """Binary little-endian PLY: float x, y, z per vertex; uchar count + int vertex indices per face.  colors (optional, [Nv,3]):
+    uchar red, green, blue per vertex behind the coordinates -- uint8 as given, floats as round(255 c) clipped to [0, 255]; without
+    it the file is the plain mesh, byte for byte."""
     V = np.ascontiguousarray(V.cpu().numpy() if torch.is_tensor(V) else V, dtype='<f4').reshape(-1, 3)
     F = np.ascontiguousarray(F.cpu().numpy() if torch.is_tensor(F) else F).reshape(-1, 3)
     if F.size and (F.min() < 0 or F.max() >= len(V)):
@@ -196,8 +198,19 @@ def write_ply(path, V, F):
     faces = np.empty(len(F), dtype=np.dtype([('n', 'u1'), ('i', '<i4', (3,))]))
     faces['n'] = 3
     faces['i'] = F
+    cprops = ""
+    if colors is not None:
+        C = np.asarray(colors.cpu().numpy() if torch.is_tensor(colors) else colors)
+        if C.shape != (len(V), 3):
+            raise ValueError(f"write_ply: colors must be [{len(V)}, 3], got {tuple(C.shape)}")
+        if C.dtype != np.uint8:
+            C = np.clip(np.rint(255.0 * C.astype(np.float64)), 0, 255).astype(np.uint8)
+        verts = np.empty(len(V), dtype=np.dtype([('p', '<f4', (3,)), ('c', 'u1', (3,))]))
+        verts['p'], verts['c'] = V, C
+        V = verts
+        cprops = "property uchar red\nproperty uchar green\nproperty uchar blue\n"
     header = ("ply\nformat binary_little_endian 1.0\n"
-              f"element vertex {len(V)}\nproperty float x\nproperty float y\nproperty float z\n"
+              f"element vertex {len(V)}\nproperty float x\nproperty float y\nproperty float z\n{cprops}"
               f"element face {len(F)}\nproperty list uchar int vertex_indices\nend_header\n")
     with open(path, 'wb') as fh:
         fh.write(header.encode('ascii'))
@@ -241,16 +254,17 @@ def _ply_header(data, path):
     return fmt, elements, body
 
 
-def read_ply(path):
+def read_ply(path, colors=False):
     """Triangle mesh from a PLY file -> (V float32 [Nv,3], F int32 [Nf,3]); the inverse of write_ply.  Reads ascii and binary
     little-endian files with float or double coordinates; other vertex properties (normals, colours) and other elements without
     lists are skipped; the face list may count in uchar / int / uint and index in int / uint.  Refuses non-triangle faces,
-    big-endian files and face indices outside the vertices."""
+    big-endian files and face indices outside the vertices.  colors=True: returns (V, F, C) with C uint8 [Nv,3] from the vertex
+    properties red / green / blue, or None when the file has none."""
     path = str(path)
     with open(path, 'rb') as fh:
         data = fh.read()
     fmt, elements, off = _ply_header(data, path)
-    V = F = None
+    V = F = C = None
     tokens = data[off:].decode('ascii', 'replace').split() if fmt == 'ascii' else None
     ti = 0
     for name, count, props in elements:
@@ -284,6 +298,9 @@ def read_ply(path):
                     rows = np.asarray(vals, np.float64).reshape(count, width)
                     cols = [[p for p, _ in props].index(c) for c in 'xyz']
                     V = rows[:, cols].astype(np.float32)
+                    names = [p for p, _ in props]
+                    if all(c in names for c in ('red', 'green', 'blue')):
+                        C = rows[:, [names.index(c) for c in ('red', 'green', 'blue')]].astype(np.uint8)
             continue
         fields = []
         for p, t in props:
@@ -301,6 +318,8 @@ def read_ply(path):
         off += count * dt.itemsize
         if name == 'vertex':
             V = np.stack([rec['x'], rec['y'], rec['z']], 1).astype(np.float32)
+            if all(c in rec.dtype.names for c in ('red', 'green', 'blue')):
+                C = np.stack([rec['red'], rec['green'], rec['blue']], 1).astype(np.uint8)
         elif name == 'face':
             F = rec['i'].astype(np.int64)
     if V is None:
@@ -309,6 +328,8 @@ def read_ply(path):
         F = np.zeros((0, 3), np.int64)
     if F.size and (F.min() < 0 or F.max() >= len(V)):
         raise ValueError(f"read_ply: {path}: face index out of range (vertices: {len(V)})")
+    if colors:
+        return np.ascontiguousarray(V), np.ascontiguousarray(F, dtype=np.int32), C
     return np.ascontiguousarray(V), np.ascontiguousarray(F, dtype=np.int32)
 
 

@@ -318,6 +318,12 @@ class NeROShapeRenderer(nn.Module):
         self._engine = None  # parameters may move: rebuild the packed tables lazily
         return super()._apply(fn, *a, **k)
 
+    def predict_materials(self, mesh=None):
+        """renderer_zerothick.py:846-864: {'metallic' [V,1], 'roughness' [V,1], 'albedo' [V,3]} (float32 numpy) at the vertices of
+        `mesh` (None: data/meshes/{name}-300000.ply; a PLY path or a (V, F) pair), baked by one fused kernel (materials.py)."""
+        from .materials import predict_materials
+        return predict_materials(self, mesh)
+
     # ---- data ----------------------------------------------------------------------------------
     def _init_dataset(self):
         """Ray-batch store (renderer_zerothick.py:167-190).  `database_name: synthetic/<n_rays>` builds the seeded synthetic

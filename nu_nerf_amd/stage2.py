@@ -197,6 +197,12 @@ class Stage2Renderer(nn.Module):
             self._nets = (n1, n2)
         return self._nets
 
+    def predict_materials(self, mesh=None, which='inner'):
+        """renderer_zerothick.py:2037-2055 names `self.sdf_network`, which the reference's Stage2Renderer never sets; here
+        which='inner' bakes sdf_network_inner + color_network_inner, which='outer' the stage-1 networks (materials.py)."""
+        from .materials import predict_materials
+        return predict_materials(self, mesh, which)
+
     def get_anneal_val(self, step):
         if self.cfg['anneal_end'] < 0:
             return 1.0
