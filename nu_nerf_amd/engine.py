@@ -27,103 +27,12 @@ import torch
 
 from . import _lib as L
 
-c_int, c_ll, c_f, c_p = ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_void_p
+# the C ABI's structs and constants, as include/nu_nerf.h declares them (re-exported: tests and scripts import them from here)
+from ._lib import (GemmNT, GemmTN, ReduceDesc, PackDesc, Lin, WgradItem, OpCtx, SdfNet, SdfBufs, NerfNet, NerfBufs, ShadeNet, BakeNet,  # noqa: F401
+                   ShadeBufs, EPI_BIAS_NONE, EPI_BIAS_RELU, EPI_BIAS_SOFTPLUS, EPI_MUL_DRELU, EPI_MUL_DSP, EPI_Q_SP, EPI_B_SP,
+                   EPI_PLAIN, EPI_B_RELU, NU_WGRAD_QUEUE_MAX)
 
-EPI_BIAS_NONE, EPI_BIAS_RELU, EPI_BIAS_SOFTPLUS, EPI_MUL_DRELU, EPI_MUL_DSP, EPI_Q_SP, EPI_B_SP, EPI_PLAIN, EPI_B_RELU = range(9)
-
-
-class GemmNT(ctypes.Structure):
-    _fields_ = [("A", c_p), ("lda", c_int), ("B", c_p), ("ldb", c_int), ("M", c_int), ("N", c_int), ("K", c_int),
-                ("C", c_p), ("ldc", c_int), ("C2", c_p), ("ldc2", c_int), ("bias", c_p), ("H", c_p), ("ldh", c_int),
-                ("D", c_p), ("ldd", c_int), ("Cadd", c_p), ("ldadd", c_int), ("zero_to", c_int), ("act_cols", c_int),
-                ("alpha", c_f), ("groups", c_int), ("sA", c_ll), ("sB", c_ll), ("sC", c_ll), ("sC2", c_ll),
-                ("sBias", c_ll), ("sH", c_ll), ("sD", c_ll), ("sCadd", c_ll), ("epi", c_int), ("bf16", c_int),
-                ("mask", c_p), ("mask_nct", c_int), ("mask_ct0", c_int), ("B6", c_p)]
-
-
-class GemmTN(ctypes.Structure):
-    _fields_ = [("A0", c_p), ("lda0", c_int), ("B0", c_p), ("ldb0", c_int), ("A1", c_p), ("lda1", c_int),
-                ("B1", c_p), ("ldb1", c_int), ("P", c_int), ("N1", c_int), ("N2", c_int), ("slab", c_p),
-                ("bias_slab", c_p), ("S", c_int), ("groups", c_int), ("sA0", c_ll), ("sB0", c_ll), ("sA1", c_ll),
-                ("sB1", c_ll), ("sSlab", c_ll), ("sBiasSlab", c_ll), ("bf16", c_int), ("pad_", c_int)]
-
-
-class ReduceDesc(ctypes.Structure):
-    """Mirror of NuReduceDesc (include/nu_nerf.h): one deferred deterministic split reduction."""
-    _fields_ = [("slab", c_p), ("out", c_p), ("ss", c_ll), ("S", c_int), ("N1", c_int), ("N2", c_int), ("rs", c_int),
-                ("ldo", c_int), ("accumulate", c_int), ("G", c_int), ("blk_begin", c_int), ("alpha", ctypes.c_float),
-                ("pad_", c_int)]
-
-
-class PackDesc(ctypes.Structure):
-    _fields_ = [("v", c_p), ("g", c_p), ("colmap", c_p), ("Wp", c_p), ("WpT", c_p), ("dWp", c_p), ("dv_off", c_ll),
-                ("dg_off", c_ll), ("bias", c_p), ("bias_p", c_p), ("scale", c_f), ("N", c_int), ("K", c_int),
-                ("Kp", c_int), ("ldT", c_int), ("ldd", c_int), ("row_begin", c_int), ("col_off", c_int), ("Wp16", c_p), ("WpT16", c_p),
-                ("planes", c_int), ("pad_", c_int), ("w6_row0", c_int), ("w6_ld", c_int), ("t6_row0", c_int), ("t6_col0", c_int),
-                ("t6_ld", c_int), ("pad2_", c_int)]
-
-
-class Lin(ctypes.Structure):
-    """Mirror of NuLin (include/nu_nerf.h): one packed layer."""
-    _fields_ = [("Wp", c_p), ("WpT", c_p), ("dWp", c_p), ("bias", c_p), ("db_off", c_ll), ("N", c_int), ("K", c_int), ("Kp", c_int),
-                ("ldT", c_int), ("ldd", c_int), ("pad_", c_int), ("Wp16", c_p), ("WpT16", c_p)]
-
-
-class WgradItem(ctypes.Structure):
-    """Mirror of NuWgradItem: one queued weight gradient of a backward pass."""
-    _fields_ = [("g", GemmTN), ("dW", c_p), ("ldw", c_int), ("pad_", c_int), ("sW", c_ll), ("db", c_p), ("sDb", c_ll),
-                ("flops", ctypes.c_double), ("bytes", ctypes.c_double)]
-
-
-class OpCtx(ctypes.Structure):
-    """Mirror of NuOpCtx: arithmetic mode, flat gradient buffer, deferred-reduction arena (shared by the Python-sequenced path),
-    the queue of a pass's weight gradients."""
-    _fields_ = [("prec", c_int), ("h16", c_int), ("flat", c_p), ("arena", c_p), ("arena_floats", c_ll), ("arena_off", c_ll),
-                ("descs", c_p), ("ndesc", c_int), ("cap", c_int), ("ev", c_p), ("ev_meta", c_p), ("nev", c_int), ("ev_cap", c_int),
-                ("forked", c_int), ("pad_", c_int), ("pend", c_p), ("npend", c_int), ("pend_cap", c_int)]
-
-
-class SdfNet(ctypes.Structure):
-    _fields_ = [("lin", Lin * 9)]
-
-
-class SdfBufs(ctypes.Structure):
-    _fields_ = [("P", c_int), ("pad_", c_int), ("E", c_p), ("U4", c_p), ("YX", c_p), ("sdf", c_p), ("H", c_p * 9), ("D", c_p * 8),
-                ("G0", c_p), ("n", c_p), ("Q", c_p * 9), ("C", c_p * 8), ("Aux", c_p * 8), ("dE0", c_p)]
-
-
-class NerfNet(ctypes.Structure):
-    _fields_ = [("pts", Lin * 8), ("feat", Lin), ("alpha", Lin), ("view", Lin), ("rgb", Lin)]
-
-
-class NerfBufs(ctypes.Structure):
-    _fields_ = [("P", c_int), ("pad_", c_int), ("H", c_p * 9), ("mask", c_p * 9), ("V", c_p), ("HV", c_p), ("sig", c_p), ("rgb", c_p),
-                ("dHV", c_p), ("dF", c_p), ("dH8a", c_p), ("dA", c_p * 9), ("dE4", c_p), ("dx", c_p), ("ddir", c_p)]
-
-
-class ShadeNet(ctypes.Structure):
-    _fields_ = [("WpM0", c_p), ("WpTM0", c_p), ("bM0", c_p), ("dWpM0", c_p), ("WpM", c_p * 3), ("WpTM", c_p * 3), ("bM", c_p * 3),
-                ("dWpM", c_p * 3), ("dbM_off", c_ll * 3), ("Ws6", c_p), ("b6", c_p), ("dWs6", c_p), ("db6_off", c_ll),
-                ("outer_light", Lin * 4), ("inner_light", Lin * 4), ("inner_weight", Lin * 4), ("refrac_light", Lin * 4),
-                ("lut", c_p), ("exp_max", c_f), ("sphere", c_int), ("ld_ol", c_int), ("refrac_dim", c_int), ("ld_rl", c_int), ("pad_", c_int),
-                ("WpM0_16", c_p), ("WpTM0_16", c_p), ("WpM16", c_p * 3), ("WpTM16", c_p * 3)]
-
-
-class BakeNet(ctypes.Structure):
-    """Mirror of NuBakeNet: the SDF network plus the packed material tables, and the debug outputs of the bake kernel."""
-    _fields_ = [("sdf", SdfNet), ("WpM0", c_p), ("bM0", c_p), ("WpM", c_p * 3), ("bM", c_p * 3), ("Ws6", c_p), ("b6", c_p),
-                ("feat", c_p), ("n_pred", c_int), ("raw", c_int)]
-
-
-class ShadeBufs(ctypes.Structure):
-    _fields_ = [("P", c_int), ("R", c_int), ("extra_dirs", c_p), ("extra_pts", c_p), ("M", c_p * 3), ("maskM", c_p * 3), ("Mraw", c_p),
-                ("OLin", c_p), ("ILin", c_p), ("IWin", c_p), ("RLin", c_p), ("SD", c_p),
-                ("OLh", c_p * 3), ("ILh", c_p * 3), ("IWh", c_p * 3), ("RLh", c_p * 3),
-                ("maskOL", c_p * 3), ("maskIL", c_p * 3), ("maskIW", c_p * 3), ("maskRL", c_p * 3),
-                ("OLo", c_p), ("ILo", c_p), ("IWo", c_p), ("RLo", c_p), ("aux", c_p),
-                ("dMraw", c_p), ("dOLo", c_p), ("dILo", c_p), ("dIWo", c_p), ("dRLo", c_p), ("dNoV", c_p),
-                ("dH3", c_p * 4), ("tmpOL", c_p * 2), ("tmpIL", c_p * 2), ("tmpIW", c_p * 2), ("tmpRL", c_p * 2),
-                ("dOLin", c_p), ("dILin", c_p), ("dn", c_p), ("dM", c_p * 3), ("dYX", c_p)]
+c_int, c_p = ctypes.c_int, ctypes.c_void_p
 
 
 def rup(a, b):
@@ -169,10 +78,6 @@ class Stage1Engine:
         self.refrac_dim = 3 + 6 * int(cfg.get('refrac_freq', 6))       # field.py:590-591 (real_bottle uses refrac_freq 3)
         self.ld_ol = 160 if self.sphere_direction else 96               # outer_light input 144 / 72 (field.py:594-597)
         self.ld_rl = rup(2 * self.refrac_dim, 32)
-        lib = self.lib
-        assert lib.nu_pack_desc_size() == ctypes.sizeof(PackDesc), "PackDesc ABI mismatch"
-        assert lib.nu_reduce_desc_size() == ctypes.sizeof(ReduceDesc), "ReduceDesc ABI mismatch"
-        assert lib.nu_gemm_nt_size() == ctypes.sizeof(GemmNT) and lib.nu_gemm_tn_size() == ctypes.sizeof(GemmTN), "GEMM ABI mismatch"
         # MLP arithmetic: 'fp32' = exact fp32 MFMA (the reference's precision); 'bf16' = operands rounded to bf16 on their
         # way into LDS, bf16 MFMA with fp32 accumulation (BASELINE config 4; no reference counterpart, tolerance in the tests)
         md = str(cfg.get('mlp_dtype', os.environ.get('NU_MLP_DTYPE', 'fp32'))).lower()   # env: run a whole test suite in one mode
@@ -192,17 +97,12 @@ class Stage1Engine:
         # one context for both sequencing paths (network-level C entries and the launch-by-launch Python path below): the
         # descriptor count and the arena offset live in the struct
         # the weight gradients of a backward pass are queued and launched together (include/nu_nerf.h: nu_wgrad_defer / _flush)
-        assert lib.nu_wgrad_item_size() == ctypes.sizeof(WgradItem), "WgradItem ABI mismatch"
-        self._pend = (WgradItem * 32)()
+        self._pend = (WgradItem * NU_WGRAD_QUEUE_MAX)()
         self._ctx = OpCtx(prec=self.bf16, h16=1 if self.h16 else 0, flat=0, arena=0, arena_floats=0, arena_off=0,
                           descs=ctypes.cast(self._rd, c_p).value, ndesc=0, cap=self._rd_cap, ev=0, ev_meta=0, nev=0, ev_cap=0,
-                          forked=0, pad_=0, pend=ctypes.cast(self._pend, c_p).value, npend=0, pend_cap=32)
+                          forked=0, pad_=0, pend=ctypes.cast(self._pend, c_p).value, npend=0, pend_cap=NU_WGRAD_QUEUE_MAX)
         self._wg_depth, self._wg_held = 0, []
         self._ndesc_p = ctypes.cast(ctypes.addressof(self._ctx) + OpCtx.ndesc.offset, ctypes.POINTER(c_int))
-        for fn, st in (("nu_op_ctx_size", OpCtx), ("nu_sdf_net_size", SdfNet), ("nu_sdf_bufs_size", SdfBufs), ("nu_nerf_net_size", NerfNet),
-                       ("nu_nerf_bufs_size", NerfBufs), ("nu_shade_net_size", ShadeNet), ("nu_shade_bufs_size", ShadeBufs),
-                       ("nu_bake_net_size", BakeNet)):
-            assert getattr(lib, fn)() == ctypes.sizeof(st), f"{st.__name__} ABI mismatch"
         # NU_PY_SEQ=1: sequence every launch from Python (the path bench.py's per-launch event timing uses)
         self.py_seq = os.environ.get('NU_PY_SEQ', '0') != '0'
         if self.py_seq and self.h16:
@@ -388,22 +288,35 @@ class Stage1Engine:
             self.grad_views[name] = (off, tuple(p[name].shape))
             self.grad_numel[name] = int(p[name].numel())
 
-        # ---- SDF network ----
-        sdf = []
-        for l in range(9):
-            pre = f'sdf_network.lin{l}'
-            v = p[pre + '.weight_v']
-            N, K = v.shape
-            Kp = 64 if l == 0 else 256
-            lay = _Layer(pre, v, p[pre + '.weight_g'], p[pre + '.bias'], N, K, Kp,
-                         scale=(1.0 / math.sqrt(2.0)) if l == 4 else 1.0)
-            lay.Wp = (z(rup(N, 128), Kp), 0)
-            ldT = 288 if l == 8 else rup(N, 32)
-            lay.WpT, lay.ldT = (z(rup(Kp, 128), ldT), 0), ldT
+        def table(name, Kp, *, norm=True, ldT=None, head=False, scale=1.0, colmap=None):
+            """One layer with tables of its own.  norm: weight-normalised (weight_v, weight_g) or a plain nn.Linear (weight); head: a
+            skinny output head -- no rows padded to the NT tile and no transposed table; ldT: rup(N, 32) unless given.  The order of
+            the galloc calls is the layout of the flat gradient buffer."""
+            wname = name + ('.weight_v' if norm else '.weight')
+            w = p[wname]
+            N, K = w.shape
+            lay = _Layer(name, w, p[name + '.weight_g'] if norm else None, p[name + '.bias'], N, K, Kp, scale=scale, colmap=colmap)
+            lay.Wp = (z(N if head else rup(N, 128), Kp), 0)
+            if not head:
+                lay.ldT = ldT or rup(N, 32)
+                lay.WpT = (z(rup(Kp, 128), lay.ldT), 0)
             lay.dWp, lay.ldd = (z(N, Kp), 0), Kp
-            lay.dv_off, lay.dg_off, lay.db_off = galloc(N * K), galloc(N), galloc(N)
-            reg(pre + '.weight_v', lay.dv_off); reg(pre + '.weight_g', lay.dg_off); reg(pre + '.bias', lay.db_off)
-            sdf.append(lay)
+            lay.dv_off = galloc(N * K)
+            reg(wname, lay.dv_off)
+            if norm:
+                lay.dg_off = galloc(N)
+                reg(name + '.weight_g', lay.dg_off)
+            lay.db_off = galloc(N)
+            reg(name + '.bias', lay.db_off)
+            return lay
+
+        def predictor(pre, modules, Kp0):
+            """make_predictor (field.py:371-408): three 256-wide hidden layers and a head, at these indices of the nn.Sequential."""
+            return [table(f'{pre}.{idx}', Kp0 if j == 0 else 256, ldT=256, head=j == 3) for j, idx in enumerate(modules)]
+
+        # ---- SDF network ----
+        sdf = [table(f'sdf_network.lin{l}', 64 if l == 0 else 256, ldT=288 if l == 8 else None,
+                     scale=(1.0 / math.sqrt(2.0)) if l == 4 else 1.0) for l in range(9)]
         self.sdf = sdf
         layers += sdf
         self.var_off = galloc(1)
@@ -413,25 +326,14 @@ class Stage1Engine:
         nerf = []
         cm5 = np.concatenate([256 + np.arange(84), np.arange(256)]).astype(np.int32)   # [emb(84), h(256)] -> h | emb
         self._colmaps = {'n5': torch.from_numpy(cm5).to(self.dev)}
-
-        def plain(name, Kp, colmap=None, NT_rows=True):
-            w = p[name + '.weight']
-            N, K = w.shape
-            lay = _Layer(name, w, None, p[name + '.bias'], N, K, Kp, colmap=colmap)
-            lay.Wp = (z(rup(N, 128), Kp), 0)
-            lay.WpT, lay.ldT = (z(rup(Kp, 128), rup(N, 32)), 0), rup(N, 32)
-            lay.dWp, lay.ldd = (z(N, Kp), 0), Kp
-            lay.dv_off, lay.db_off = galloc(N * K), galloc(N)
-            reg(name + '.weight', lay.dv_off); reg(name + '.bias', lay.db_off)
-            return lay
         for i in range(8):
             Kp = 96 if i == 0 else (352 if i == 5 else 256)
-            nerf.append(plain(f'outer_nerf.pts_linears.{i}', Kp, self._colmaps['n5'] if i == 5 else None))
+            nerf.append(table(f'outer_nerf.pts_linears.{i}', Kp, norm=False, colmap=self._colmaps['n5'] if i == 5 else None))
         self.nerf = nerf
-        self.nerf_feat = plain('outer_nerf.feature_linear', 256)
-        self.nerf_alpha = plain('outer_nerf.alpha_linear', 256)
-        self.nerf_view = plain('outer_nerf.views_linears.0', 288)
-        self.nerf_rgb = plain('outer_nerf.rgb_linear', 128)
+        self.nerf_feat = table('outer_nerf.feature_linear', 256, norm=False)
+        self.nerf_alpha = table('outer_nerf.alpha_linear', 256, norm=False)
+        self.nerf_view = table('outer_nerf.views_linears.0', 288, norm=False)
+        self.nerf_rgb = table('outer_nerf.rgb_linear', 128, norm=False)
         self.nerf_all = nerf + [self.nerf_feat, self.nerf_alpha, self.nerf_view, self.nerf_rgb]     # consecutive in the table
         layers += self.nerf_all
 
@@ -483,27 +385,10 @@ class Stage1Engine:
         layers += self.mat_layers
 
         # ---- shading: light predictors ----
-        def predictor(name, Kp0):
-            pre = f'color_network.{name}'
-            out = []
-            for j, idx in enumerate((0, 2, 4, 6)):
-                q = f'{pre}.{idx}'
-                v = p[q + '.weight_v']
-                N, K = v.shape
-                Kp = Kp0 if j == 0 else 256
-                lay = _Layer(q, v, p[q + '.weight_g'], p[q + '.bias'], N, K, Kp)
-                lay.Wp = (z(rup(N, 128) if j < 3 else N, Kp), 0)
-                if j < 3:
-                    lay.WpT, lay.ldT = (z(rup(Kp, 128), 256), 0), 256
-                lay.dWp, lay.ldd = (z(N, Kp), 0), Kp
-                lay.dv_off, lay.dg_off, lay.db_off = galloc(N * K), galloc(N), galloc(N)
-                reg(q + '.weight_v', lay.dv_off); reg(q + '.weight_g', lay.dg_off); reg(q + '.bias', lay.db_off)
-                out.append(lay)
-            return out
-        self.outer_light = predictor('outer_light', self.ld_ol)
-        self.inner_light = predictor('inner_light', 128)
-        self.inner_weight = predictor('inner_weight', 96)
-        self.refrac_light = predictor('refrac_light', self.ld_rl)
+        self.outer_light = predictor('color_network.outer_light', (0, 2, 4, 6), self.ld_ol)
+        self.inner_light = predictor('color_network.inner_light', (0, 2, 4, 6), 128)
+        self.inner_weight = predictor('color_network.inner_weight', (0, 2, 4, 6), 96)
+        self.refrac_light = predictor('color_network.refrac_light', (0, 2, 4, 6), self.ld_rl)
         layers += self.outer_light + self.inner_light + self.inner_weight + self.refrac_light
         # ---- stage 2: the IoR / thickness networks (field.py:1046-1087: 39 -> 256 ReLU -> 256 ReLU -> 256 -> 1), when the owner
         # has them ----
@@ -511,22 +396,8 @@ class Stage1Engine:
         for pre in ('ior_network', 'thickness_network'):
             if pre + '.0.weight_v' not in p:
                 continue
-            net = []
-            for j, idx in enumerate((0, 2, 4, 5)):
-                q = f'{pre}.{idx}'
-                v = p[q + '.weight_v']
-                N, K = v.shape
-                Kp = 64 if j == 0 else 256
-                lay = _Layer(q, v, p[q + '.weight_g'], p[q + '.bias'], N, K, Kp)
-                lay.Wp = (z(rup(N, 128) if j < 3 else N, Kp), 0)
-                if j < 3:
-                    lay.WpT, lay.ldT = (z(rup(Kp, 128), 256), 0), 256
-                lay.dWp, lay.ldd = (z(N, Kp), 0), Kp
-                lay.dv_off, lay.dg_off, lay.db_off = galloc(N * K), galloc(N), galloc(N)
-                reg(q + '.weight_v', lay.dv_off); reg(q + '.weight_g', lay.dg_off); reg(q + '.bias', lay.db_off)
-                net.append(lay)
-            self.small[pre] = net
-            layers += net
+            self.small[pre] = predictor(pre, (0, 2, 4, 5), 64)
+            layers += self.small[pre]
         self.ior = self.small.get('ior_network')
         self.layers = layers
         self.n_grad = self._goff

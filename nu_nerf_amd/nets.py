@@ -13,7 +13,7 @@ per-bounce bookkeeping of stage 2 can stay in torch while every GEMM runs in the
 """
 import torch
 
-from .engine import addr
+from .engine import EPI_BIAS_NONE, EPI_BIAS_RELU, EPI_MUL_DRELU, EPI_PLAIN, addr
 
 
 def _numel(shape):
@@ -189,7 +189,6 @@ class StacksFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eng, stacks, layers_union, names, token, *Xs):
-        from .engine import EPI_BIAS_RELU
         Xps, Hss = [], []
         for layers, X in zip(stacks, Xs):
             rows, K = X.shape
@@ -218,7 +217,6 @@ class StacksFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *douts):
-        from .engine import EPI_MUL_DRELU, EPI_PLAIN
         eng, stacks, Xps, Hss = ctx.eng, ctx.stacks, ctx.Xps, ctx.Hss
         eng.op_begin()
         flat = eng.zeros(eng.n_grad)
@@ -261,7 +259,6 @@ class MaterialsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eng, feat, x, names, token):
-        from .engine import EPI_BIAS_RELU
         P = feat.shape[0]
         YX = eng.zeros(P, 288)
         YX[:, 1:257] = feat.detach()
@@ -281,7 +278,6 @@ class MaterialsFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dM):
-        from .engine import EPI_MUL_DRELU, EPI_PLAIN
         eng, s = ctx.eng, ctx.s
         eng.op_begin()
         P = s['YX'].shape[0]
@@ -319,7 +315,6 @@ class IorFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eng, ls, X, names, token):
-        from .engine import EPI_BIAS_NONE, EPI_BIAS_RELU
         rows, K = X.shape
         Xp = eng.zeros(rows, 64)
         Xp[:, :K] = X.detach()
@@ -335,7 +330,6 @@ class IorFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        from .engine import EPI_MUL_DRELU, EPI_PLAIN
         eng, ls, Xp, H = ctx.eng, ctx.ls, ctx.Xp, ctx.H
         eng.op_begin()
         rows = Xp.shape[0]
@@ -369,7 +363,6 @@ class IorPairFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, eng, la, lb, X, names, token):
-        from .engine import EPI_BIAS_NONE, EPI_BIAS_RELU
         rows, K = X.shape
         Xp = eng.zeros(rows, 64)
         Xp[:, :K] = X.detach()
@@ -391,7 +384,6 @@ class IorPairFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, da, db):
-        from .engine import EPI_MUL_DRELU, EPI_PLAIN
         eng, la, lb, Xp, H = ctx.eng, ctx.la, ctx.lb, ctx.Xp, ctx.H
         eng.op_begin()
         rows = Xp.shape[0]

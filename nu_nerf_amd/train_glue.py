@@ -8,8 +8,6 @@
   train_step                       the loop body of Trainer_zero.run (train/trainer_zero.py:131-161) + the gradient
                                    all-reduce of the data-parallel build
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -55,12 +53,6 @@ class WarmUpCosLR(LearningRateManager):
 name2lr_manager = {'warm_up_cos': WarmUpCosLR}
 
 
-class AdamDesc(ctypes.Structure):
-    """Mirror of NuAdamDesc (include/nu_nerf.h)."""
-    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
-                ("n", ctypes.c_longlong), ("blk_begin", ctypes.c_int), ("pad_", ctypes.c_int)]
-
-
 class FusedAdam(torch.optim.Optimizer):
     """Adam (no weight decay, no amsgrad: what the reference trains with) on the HIP multi-tensor kernel.  Parameters
     without a gradient are skipped like torch.optim.Adam does; every parameter group keeps its own lr / betas / eps and
@@ -75,7 +67,6 @@ class FusedAdam(torch.optim.Optimizer):
     def _library(self):
         if self._lib is None:
             self._lib = L.load()
-            assert self._lib.nu_adam_desc_size() == ctypes.sizeof(AdamDesc), "AdamDesc ABI mismatch"
         return self._lib
 
     def load_state_dict(self, state_dict):
@@ -120,7 +111,7 @@ class FusedAdam(torch.optim.Optimizer):
             buckets.setdefault(int(view), []).append((p, st, slot))
         plan = []
         for count, items in buckets.items():
-            descs = (AdamDesc * len(items))()
+            descs = (L.AdamDesc * len(items))()
             for d, (p, st, _) in zip(descs, items):
                 d.p, d.m, d.v, d.n = p.data_ptr(), st['exp_avg'].data_ptr(), st['exp_avg_sq'].data_ptr(), p.numel()
             plan.append({'count': count, 'params': [p for p, _, _ in items], 'descs': descs,

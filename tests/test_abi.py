@@ -44,16 +44,109 @@ def test_library_exports_every_declared_symbol(lib):
     assert not missing, missing
 
 
-def test_struct_layouts_match_python_mirrors(lib):
+# sizeof of every struct of include/nu_nerf.h under the natural alignment of the x86-64 / amdgcn ABIs, and offsets a size cannot see
+# (two fields swapped, a pointer for a long long).  Literals on purpose: they depend neither on the header reader nor on the library.
+STRUCT_BYTES = {"GemmNT": 240, "GemmTN": 152, "ReduceDesc": 64, "PackDesc": 160, "Lin": 80, "WgradItem": 208, "OpCtx": 104,
+                "SdfNet": 720, "SdfBufs": 400, "NerfNet": 960, "NerfBufs": 304, "ShadeNet": 1560, "ShadeBufs": 552, "BakeNet": 816,
+                "AdamDesc": 48}
+SIZE_ENTRIES = {"nu_gemm_nt_size": 240, "nu_gemm_tn_size": 152, "nu_reduce_desc_size": 64, "nu_pack_desc_size": 160,
+                "nu_wgrad_item_size": 208, "nu_op_ctx_size": 104, "nu_sdf_net_size": 720, "nu_sdf_bufs_size": 400,
+                "nu_nerf_net_size": 960, "nu_nerf_bufs_size": 304, "nu_shade_net_size": 1560, "nu_shade_bufs_size": 552,
+                "nu_bake_net_size": 816, "nu_adam_desc_size": 48}
+FIELD_OFFSETS = {"GemmNT.lda": 8, "GemmNT.epi": 208, "GemmNT.bf16": 212, "GemmNT.mask": 216, "GemmNT.B6": 232, "GemmTN.bf16": 144,
+                 "ReduceDesc.alpha": 56, "PackDesc.w6_row0": 136, "WgradItem.dW": 152, "OpCtx.ndesc": 48, "OpCtx.pend": 88,
+                 "SdfBufs.Q": 192, "NerfBufs.dA": 208, "ShadeNet.lut": 1464, "ShadeBufs.dYX": 544, "BakeNet.feat": 800, "AdamDesc.n": 32}
+
+
+def test_struct_layouts_read_from_the_header():
+    """The ctypes structs come from include/nu_nerf.h (nu_nerf_amd/_lib.py); no library and no GPU is needed to build them."""
+    from nu_nerf_amd import _lib, engine
+    assert set(_lib.STRUCTS) == set(STRUCT_BYTES)
+    for name, nbytes in STRUCT_BYTES.items():
+        assert ctypes.sizeof(getattr(_lib, name)) == nbytes, name
+        assert getattr(_lib, name) is _lib.STRUCTS[name] and issubclass(_lib.STRUCTS[name], ctypes.Structure)
+    for path, off in FIELD_OFFSETS.items():
+        st, field = path.split(".")
+        assert getattr(getattr(_lib, st), field).offset == off, path
+    # what the engine builds positionally and the tests / scripts import from it
+    assert engine.GemmNT is _lib.GemmNT and engine.GemmTN is _lib.GemmTN and engine.BakeNet is _lib.BakeNet
+    assert [f for f, _ in _lib.Lin._fields_] == ["Wp", "WpT", "dWp", "bias", "db_off", "N", "K", "Kp", "ldT", "ldd", "pad_", "Wp16", "WpT16"]
+    assert [f for f, _ in _lib.GemmNT._fields_][:9] == ["A", "lda", "B", "ldb", "M", "N", "K", "C", "ldc"]
+    assert _lib.GemmNT.A.size == 8 and _lib.GemmNT.alpha.size == 4 and _lib.GemmNT.sA.size == 8 and _lib.WgradItem.g.size == 152
+    assert _lib.SdfBufs.H.size == 72 and _lib.SdfNet.lin.size == 720 and _lib.ShadeNet.dbM_off.size == 24
+
+
+def test_compiled_struct_sizes(lib):
+    """Every nu_*_size entry of the header against the literal: the library agrees with the table above, hence with the structs."""
+    assert sorted(n for n in declared_functions() if n.endswith("_size")) == sorted(SIZE_ENTRIES)
+    for fn, nbytes in SIZE_ENTRIES.items():
+        assert getattr(lib, fn)() == nbytes, fn
     from nu_nerf_amd.engine import PackDesc, GemmNT, GemmTN
     assert lib.nu_pack_desc_size() == ctypes.sizeof(PackDesc)
-    # natural-alignment sizes of the C structs in include/nu_nerf.h
     assert ctypes.sizeof(GemmNT) == 240 and ctypes.sizeof(GemmTN) == 152
-    assert lib.nu_gemm_nt_size() == 240 and lib.nu_gemm_tn_size() == 152 and lib.nu_reduce_desc_size() == 64
     from nu_nerf_amd.engine import OpCtx, SdfNet, SdfBufs, NerfNet, NerfBufs, ShadeNet, ShadeBufs
     for fn, st in (("nu_op_ctx_size", OpCtx), ("nu_sdf_net_size", SdfNet), ("nu_sdf_bufs_size", SdfBufs), ("nu_nerf_net_size", NerfNet),
                    ("nu_nerf_bufs_size", NerfBufs), ("nu_shade_net_size", ShadeNet), ("nu_shade_bufs_size", ShadeBufs)):
         assert getattr(lib, fn)() == ctypes.sizeof(st), fn
+
+
+def test_header_constants():
+    from nu_nerf_amd import _lib, engine
+    epi = ("BIAS_NONE", "BIAS_RELU", "BIAS_SOFTPLUS", "MUL_DRELU", "MUL_DSP", "Q_SP", "B_SP", "PLAIN", "B_RELU")
+    for value, name in enumerate(epi):
+        assert getattr(_lib, "EPI_" + name) == value and getattr(_lib, "NU_EPI_" + name) == value and getattr(engine, "EPI_" + name) == value
+    assert _lib.NU_EPI_COUNT == 9
+    assert (_lib.NU_OK, _lib.NU_ERR_ARG, _lib.NU_ERR_LAUNCH, _lib.NU_ERR_WORKSPACE) == (0, -1, -2, -3)
+    assert (_lib.NU_GEMM_PRESPLIT_ALWAYS, _lib.NU_GEMM_B16, _lib.NU_GEMM_A16, _lib.NU_GEMM_C16, _lib.NU_GEMM_X16) == (4, 8, 16, 32, 64)
+    assert (_lib.NU_TN_A0_16, _lib.NU_TN_B0_16, _lib.NU_TN_A1_16, _lib.NU_TN_B1_16) == (16, 32, 64, 128)
+    assert (_lib.NU_REDUCE_MAX, _lib.NU_NT_BATCH_MAX, _lib.NU_WGRAD_QUEUE_MAX, _lib.NU_ADAM_MAX) == (48, 8, 32, 80)
+    assert not hasattr(_lib, "NU_RM_ARGS") and not hasattr(_lib, "NU_NERF_H")          # no integers: not constants
+
+
+@pytest.mark.parametrize("text,names", [
+    ("typedef struct NuBad { int n; short x; } NuBad;", ("NuBad", "x", "short")),                 # a type the reader does not map
+    ("typedef struct NuBad { float* p; unsigned y; } NuBad;", ("NuBad", "y", "unsigned")),
+    ("typedef struct NuBad { NuLater z; } NuBad; typedef struct NuLater { int a; } NuLater;", ("NuBad", "z", "NuLater")),
+    ("typedef struct NuBad { float* H[NU_NOT_DEFINED]; } NuBad;", ("NuBad", "H", "NU_NOT_DEFINED")),     # array bounds
+    ("typedef struct NuBad { int v[NU_ZERO]; } NuBad;", ("NuBad", "v", "NU_ZERO")),
+    ("typedef struct NuBad { int v[2 + 2]; } NuBad;", ("NuBad", "v")),                              # declarator shapes
+    ("typedef struct NuBad { int (*fn)(int); } NuBad;", ("NuBad", "fn")),
+    ("typedef struct NuBad { int bits : 3; } NuBad;", ("NuBad", "bits")),
+    ("typedef struct NuBad { int a; } NuOther;", ("NuBad", "NuOther")),
+    ("typedef struct NuBad { int a; union { int b; float c; } u; } NuBad;", ("NuBad",)),         # nested bodies are not skipped
+    ("struct NuBad { int a; };", ("NuBad",)),
+])
+def test_header_reader_fails_closed(text, names):
+    from nu_nerf_amd._lib import NuNerfLibraryError, _structs
+    with pytest.raises(NuNerfLibraryError) as err:
+        _structs(text, {"NU_FOUR": 4, "NU_ZERO": 0})
+    for name in names:
+        assert name in str(err.value), (name, str(err.value))
+
+
+def test_header_reader_maps_what_the_header_uses():
+    from nu_nerf_amd._lib import _structs
+    got = _structs("typedef struct NuIn { const float *a, *b; float c, *d; unsigned long long* m; double e; void** v; } NuIn;"
+                   "typedef struct NuOut { NuIn one, two[NU_FOUR]; long long s[3]; const NuIn* p; int n; } NuOut;", {"NU_FOUR": 4})
+    assert [(f, t.__name__) for f, t in got["In"]._fields_] == [("a", "c_void_p"), ("b", "c_void_p"), ("c", "c_float"), ("d", "c_void_p"),
+                                                                ("m", "c_void_p"), ("e", "c_double"), ("v", "c_void_p")]
+    assert ctypes.sizeof(got["In"]) == 56 and got["In"].c.offset == 16 and got["In"].d.offset == 24
+    assert ctypes.sizeof(got["Out"]) == 56 * 5 + 24 + 8 + 8 and got["Out"].two.offset == 56 and got["Out"].s.offset == 280
+    assert got["Out"]._fields_[0][1] is got["In"]
+
+
+def test_load_rejects_a_struct_whose_compiled_size_differs(lib, monkeypatch):
+    """load() compares every struct with its nu_*_size entry: a header out of step with the library is an error naming the struct."""
+    from nu_nerf_amd import _lib
+    grown = type("AdamDesc", (ctypes.Structure,), {"_fields_": list(_lib.AdamDesc._fields_) + [("extra", ctypes.c_longlong)]})
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setitem(_lib.STRUCTS, "AdamDesc", grown)
+    with pytest.raises(_lib.NuNerfLibraryError, match=r"NuAdamDesc.*nu_adam_desc_size\(\) = 48.*56"):
+        _lib.load()
+    monkeypatch.setitem(_lib.STRUCTS, "Orphan", grown)               # a struct without a size entry (other than NuLin)
+    monkeypatch.setitem(_lib.STRUCTS, "AdamDesc", _lib.AdamDesc)
+    with pytest.raises(_lib.NuNerfLibraryError, match=r"no nu_\*_size entry for struct NuOrphan"):
+        _lib.load()
 
 
 def test_workspace_queries_are_pure_host_functions(lib):

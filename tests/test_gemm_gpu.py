@@ -8,6 +8,8 @@ import ctypes
 import pytest
 import torch
 
+from nu_nerf_amd._lib import NU_GEMM_PRESPLIT_ALWAYS, NU_TN_A0_16 as A0_16, NU_TN_A1_16 as A1_16, NU_TN_B0_16 as B0_16, NU_TN_B1_16 as B1_16
+
 pytestmark = pytest.mark.gpu
 
 
@@ -458,9 +460,10 @@ def test_bf16_storage_nt_grouped_and_sign_bits(gpu):
     torch.testing.assert_close(out.double(), want, rtol=8e-3, atol=1e-3)
 
 
-@pytest.mark.parametrize("P,N1,N2,S,flags", [(1000, 257, 256, 7, 16 | 32 | 64 | 128), (5000, 256, 96, 16, 16 | 128), (333, 3, 256, 4, 32 | 64),
-                                             (3001, 256, 256, 5, 16 | 32 | 64 | 128), (2000, 512, 256, 3, 32 | 64), (777, 256, 512, 2, 0),
-                                             (60001, 256, 256, 200, 16 | 32 | 64 | 128), (50000, 512, 256, 100, 32 | 64)])   # 256-tile kernel
+@pytest.mark.parametrize("P,N1,N2,S,flags", [(1000, 257, 256, 7, A0_16 | B0_16 | A1_16 | B1_16), (5000, 256, 96, 16, A0_16 | B1_16),
+                                             (333, 3, 256, 4, B0_16 | A1_16), (3001, 256, 256, 5, A0_16 | B0_16 | A1_16 | B1_16),
+                                             (2000, 512, 256, 3, B0_16 | A1_16), (777, 256, 512, 2, 0),
+                                             (60001, 256, 256, 200, A0_16 | B0_16 | A1_16 | B1_16), (50000, 512, 256, 100, B0_16 | A1_16)])   # 256-tile kernel
 def test_bf16_storage_tn_weight_grad(gpu, P, N1, N2, S, flags):
     from nu_nerf_amd import _lib as L
     from nu_nerf_amd.engine import GemmTN, addr
@@ -468,7 +471,7 @@ def test_bf16_storage_tn_weight_grad(gpu, P, N1, N2, S, flags):
     torch.manual_seed(P)
     lda, ldb = (N1 + 7) // 8 * 8 + 8, (N2 + 7) // 8 * 8
     ops = [torch.randn(P, ld, device=gpu) for ld in (lda, ldb, lda, ldb)]
-    st = [o.bfloat16() if flags & f else o for o, f in zip(ops, (16, 32, 64, 128))]
+    st = [o.bfloat16() if flags & f else o for o, f in zip(ops, (A0_16, B0_16, A1_16, B1_16))]
     wsb = lib.nu_wgrad_workspace_bytes(N1, N2, S, 1)
     ws = torch.empty(wsb // 4, device=gpu)
     C = torch.full((N1, N2), float("nan"), device=gpu)
@@ -568,8 +571,8 @@ def test_bf16x6_presplit_weight_planes_give_the_same_bits(gpu, M, N, K, groups):
             g = GemmNT(addr(A), K * groups, addr(W), K, M, N, K, addr(C), ldc, addr(C2) if epi == 5 else 0, ldc,
                        addr(bias) if epi <= 2 else 0, addr(H) if H is not None else 0, ncol, addr(D) if epi == 5 else 0, ncol,
                        addr(Cadd) if epi in (6, 8) else 0, ncol, Np if groups == 1 and epi != 5 else 0, 0, 1.0, groups,
-                       K, Np * K, Np, Np, N, Np, Np, Np, epi, 2 | (4 if use6 else 0), mask.data_ptr() if uses_mask else 0,
-                       nct if uses_mask else 0, 0, addr(B6) if use6 else 0)                # 4: NU_GEMM_PRESPLIT_ALWAYS
+                       K, Np * K, Np, Np, N, Np, Np, Np, epi, 2 | (NU_GEMM_PRESPLIT_ALWAYS if use6 else 0), mask.data_ptr() if uses_mask else 0,
+                       nct if uses_mask else 0, 0, addr(B6) if use6 else 0)
             L.check(lib.nu_gemm_nt_ex(ctypes.byref(g), L.stream()), "nu_gemm_nt_ex epi %d" % epi)
             outs += [C, C2]
         outs.append(mask)
