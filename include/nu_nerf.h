@@ -346,6 +346,39 @@ int nu_mask_erode(const unsigned char* m, int n, int h, int w, int k, void* work
                   hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Relighting of the baked mesh under a lat-long HDR environment (relight.py -> blender_backend/relight_backend.py; the light transport
+ * is the project's own).  All launches on `stream`, no allocation, no atomics: results are the same bits from
+ * run to run and however pixels, images and sample ranges are chunked.
+ *   G-buffer row (20 floats): t, hit point [3], geometric normal [3], shading normal [3], albedo [3], metallic, roughness, view vector
+ *   [3], image index, pixel index y * w + x (the last two as int bits).  Unit normals; the geometric one faces the viewer, the shading
+ *   one (barycentric mix of vnormals [V,3]) lies on its side.  materials [V,5] = albedo, metallic, roughness per vertex.
+ *   nu_relight_gbuffer     rows [y0, y0 + rows) of n_img images (cams as nu_mask_pinhole_trace, image i hashes as img0 + i): closest hit
+ *                          of the pixel centre -> face [n_img, rows, w] (face id, 10000000 on a miss; face id and t are those of
+ *                          nu_lbvh_trace, bit for bit) and gbuf [n_img, rows, w, 20] (zero on a miss).
+ *   nu_relight_visibility  pix [n_pix] = G-buffer rows of HIT pixels; samples [s0, s0 + s_count) of `samples` (even): the shadow ray of
+ *                          (pixel, sample) -- origin = hit point + eps * geometric normal, direction = sample s of the pixel, see
+ *                          DESIGN 20 -- is made in registers and traced any-hit, tmin = 0, tmax = 1e16.  vis [n_pix, s_count] uint8:
+ *                          1 = unoccluded, 0 = occluded or not traced (direction below the shading or the geometric horizon).
+ *                          n_pix * ceil(s_count / 16) must stay below 2^31.
+ *   nu_relight_resolve     out [rows of the G-buffer, 4] += per listed pixel, in sample order, scale * weight * radiance of every sample
+ *                          with vis = 1 (rgb); alpha = 1.  env [env_h, env_w, 4] RGBA fp32, 16-byte aligned.  The caller zeroes out
+ *                          before the first sample range and passes scale = 2 / samples.
+ *   nu_relight_shadow_rays the rays nu_relight_visibility traces, rays [n_pix * s_count, 6]; bits (may be NULL) [n_pix * s_count, 3] =
+ *                          the two 24-bit sample integers, 1 where the ray is traced (tests; not on the hot path)
+ *   nu_relight_env_lookup  out [N,3] = the bilinear environment lookup of resolve at dirs [N,3] (tests)
+ * --------------------------------------------------------------------------------------------------------- */
+int nu_relight_gbuffer(const void* bvh, int n_faces, const float* V, const int* F, const float* vnormals, const float* materials,
+                       const float* cams, int n_img, int img0, int h, int w, int y0, int rows, int* face, float* gbuf,
+                       hipStream_t stream);
+int nu_relight_visibility(const void* bvh, int n_faces, const float* gbuf, const int* pix, int n_pix, int samples, int s0, int s_count,
+                          int seed, float eps, unsigned char* vis, hipStream_t stream);
+int nu_relight_resolve(const float* gbuf, const int* pix, int n_pix, int samples, int s0, int s_count, int seed, const float* env,
+                       int env_h, int env_w, const unsigned char* vis, float scale, float* out, hipStream_t stream);
+int nu_relight_shadow_rays(const float* gbuf, const int* pix, int n_pix, int samples, int s0, int s_count, int seed, float eps,
+                           float* rays, int* bits, hipStream_t stream);
+int nu_relight_env_lookup(const float* env, int env_h, int env_w, const float* dirs, int N, float* out, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Validation metrics (network/metrics.py): PSNR and SSIM of uint8 images [n, h, w, c], channel-interleaved, c in {1, 3}.
  * Pointers need no alignment.  DESIGN.md section 18 has the exactness argument and the reduction order.
  * --------------------------------------------------------------------------------------------------------- */

@@ -12,6 +12,7 @@
 // ray/triangle test below is written with explicit single-rounding fp32 operations in a fixed order, ties in t go
 // to the lowest face id, and boxes are padded so that traversal never culls a triangle the test would accept.
 #include "nu_common.h"
+#include "relight.h"
 #include <stdlib.h>
 
 // Bit-exact parity with the oracle needs one rounding per operation.  HIP's __fmul_rn/__fadd_rn are header-defined
@@ -598,6 +599,138 @@ extern "C" int nu_mask_pinhole_rays(const float* cams, int n_img, int h, int w, 
     if (N == 0) return NU_OK;
     if (nu_cdivl(N, 256) > 0x7fffffffLL) return NU_ERR_ARG;
     hipLaunchKernelGGL(mask_pinhole_rays_kernel, dim3((unsigned)nu_cdivl(N, 256)), dim3(256), 0, stream, cams, n_img, h, w, rays);
+    return nu_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------
+// relighting: the two traced passes.  Their ray sources instantiate the traversal template, so they live in this file;
+// the sample sequence, the shadow ray and the shading are relight.h, the resolve pass and the debug entries relight.hip.
+// ------------------------------------------------------------------------------------------------
+struct NuRelightPrimary {                  // pixel centres of rows [y0, y0 + rows) of n images -> face id + G-buffer row: nu_relight_gbuffer
+    const float* __restrict__ cams;        // [n, NU_CAM_FLOATS]
+    int img0, h, w, y0, rows, tiles_x, tiles;
+    const float* __restrict__ V;
+    const int* __restrict__ F;
+    const float* __restrict__ VN;          // [V,3] unit vertex normals
+    const float* __restrict__ mat;         // [V,5] albedo, metallic, roughness
+    int* __restrict__ face;                // [n, rows, w]
+    float* __restrict__ gbuf;              // [n, rows, w, NU_RL_ROW]
+    long long p;
+    int img, pixel;
+    float ro[3], rd[3];
+    __device__ __forceinline__ bool begin(int blk, int q, float* o, float* d) {
+        img = blk / tiles;
+        const int t = blk - img * tiles;
+        const int ty = t / tiles_x, tx = t - ty * tiles_x;
+        const int x = tx * 4 + (q & 3), yl = ty * 4 + (q >> 2);
+        if (x >= w || yl >= rows) return false;
+        p = ((long long)img * rows + yl) * w + x;
+        pixel = (y0 + yl) * w + x;
+        nu_pinhole_ray(cams + (long long)img * NU_CAM_FLOATS, x, y0 + yl, o, d);
+        for (int k = 0; k < 3; ++k) { ro[k] = o[k]; rd[k] = d[k]; }
+        return true;
+    }
+    __device__ __forceinline__ void end(int found, int id, float t) {
+        float* g = gbuf + p * NU_RL_ROW;
+        face[p] = found ? id : NU_RL_MISS;
+        if (!found) {
+            for (int k = 0; k < NU_RL_ROW; ++k) g[k] = 0.0f;
+            return;
+        }
+        const int i0 = F[id * 3LL], i1 = F[id * 3LL + 1], i2 = F[id * 3LL + 2];
+        float v0[3], e1[3], e2[3], pv[3], tv[3], qv[3], view[3];
+        for (int k = 0; k < 3; ++k) {
+            v0[k] = V[i0 * 3LL + k];
+            e1[k] = V[i1 * 3LL + k] - v0[k];
+            e2[k] = V[i2 * 3LL + k] - v0[k];
+            view[k] = -rd[k];
+        }
+        // the barycentrics of the accepted hit: the operations of nu_ray_tri in its order
+        nu_cross_rn(rd, e2, pv);
+        const float inv = 1.0f / nu_dot3_rn(e1, pv);
+        for (int k = 0; k < 3; ++k) tv[k] = ro[k] - v0[k];
+        const float u = nu_dot3_rn(tv, pv) * inv;
+        nu_cross_rn(tv, e1, qv);
+        const float v = nu_dot3_rn(rd, qv) * inv;
+        const float w0 = (1.0f - u) - v;
+        float ng[3], ns[3];
+        nu_cross_rn(e1, e2, ng);
+        float len = sqrtf(nu_dot3_rn(ng, ng));
+        if (len > 0.0f) { for (int k = 0; k < 3; ++k) ng[k] = ng[k] / len; }
+        else { for (int k = 0; k < 3; ++k) ng[k] = view[k]; }
+        if (nu_dot3_rn(ng, view) < 0.0f) { for (int k = 0; k < 3; ++k) ng[k] = -ng[k]; }
+        for (int k = 0; k < 3; ++k) ns[k] = (w0 * VN[i0 * 3LL + k] + u * VN[i1 * 3LL + k]) + v * VN[i2 * 3LL + k];
+        len = sqrtf(nu_dot3_rn(ns, ns));
+        if (len > 0.0f && len < 1e30f) { for (int k = 0; k < 3; ++k) ns[k] = ns[k] / len; }      // false for NaN normals too
+        else { for (int k = 0; k < 3; ++k) ns[k] = ng[k]; }
+        if (nu_dot3_rn(ns, ng) < 0.0f) { for (int k = 0; k < 3; ++k) ns[k] = -ns[k]; }
+        g[0] = t;
+        for (int k = 0; k < 3; ++k) {
+            g[1 + k] = ro[k] + t * rd[k];
+            g[4 + k] = ng[k];
+            g[7 + k] = ns[k];
+            g[15 + k] = view[k];
+        }
+        for (int k = 0; k < 5; ++k) g[10 + k] = (w0 * mat[i0 * 5LL + k] + u * mat[i1 * 5LL + k]) + v * mat[i2 * 5LL + k];
+        g[18] = __int_as_float(img0 + img);
+        g[19] = __int_as_float(pixel);
+    }
+};
+
+extern "C" int nu_relight_gbuffer(const void* bvh, int n_faces, const float* V, const int* F, const float* vnormals, const float* materials,
+                                  const float* cams, int n_img, int img0, int h, int w, int y0, int rows, int* face, float* gbuf,
+                                  hipStream_t stream) {
+    if (n_img < 0 || h <= 0 || w <= 0 || n_faces <= 0 || y0 < 0 || rows < 0 || y0 + rows > h || img0 < 0) return NU_ERR_ARG;
+    if (!bvh || !V || !F || !vnormals || !materials || !cams || !face || !gbuf) return NU_ERR_ARG;
+    if (n_img == 0 || rows == 0) return NU_OK;
+    const int tiles_x = nu_cdiv(w, 4), tiles_y = nu_cdiv(rows, 4);
+    const long long blocks = (long long)n_img * tiles_x * tiles_y;
+    if (blocks > 0x7fffffffLL || (long long)h * w > 0x7fffffffLL) return NU_ERR_ARG;       // the caller chunks over images / rows
+    const NuBvhLayout L = nu_bvh_layout(n_faces);
+    NuRelightPrimary src = {};
+    src.cams = cams; src.img0 = img0; src.h = h; src.w = w; src.y0 = y0; src.rows = rows; src.tiles_x = tiles_x; src.tiles = tiles_x * tiles_y;
+    src.V = V; src.F = F; src.VN = vnormals; src.mat = materials; src.face = face; src.gbuf = gbuf;
+    hipLaunchKernelGGL((lbvh_trace_quad_kernel<NuRelightPrimary, false>), dim3((unsigned)blocks), dim3(64), 0, stream, (const char*)bvh, L,
+                       src, 0.0f, 1e16f);
+    return nu_launch_status();
+}
+
+struct NuRelightShadow {                   // samples [s0, s0 + s_count) of the listed pixels -> one byte each (1 = lit): nu_relight_visibility
+    const float* __restrict__ gbuf;
+    const int* __restrict__ pix;           // [n_pix] G-buffer rows of hit pixels
+    int S, s0, s_count, bpp;               // bpp = 16-sample blocks per pixel
+    unsigned seed;
+    float eps;
+    unsigned char* __restrict__ vis;       // [n_pix, s_count]
+    long long slot;
+    __device__ __forceinline__ bool begin(int blk, int q, float* o, float* d) {
+        const int i = blk / bpp;
+        const int c = (blk - i * bpp) * 16 + q;
+        if (c >= s_count) return false;
+        slot = (long long)i * s_count + c;
+        unsigned bits[2];
+        if (!nu_relight_shadow_ray(gbuf + (long long)pix[i] * NU_RL_ROW, S, s0 + c, seed, eps, o, d, bits)) {
+            if ((threadIdx.x & 3) == 0) vis[slot] = 0;         // below a horizon: not traced, dark
+            return false;
+        }
+        return true;
+    }
+    __device__ __forceinline__ void end(int found, int, float) { vis[slot] = found ? 0 : 1; }
+};
+
+extern "C" int nu_relight_visibility(const void* bvh, int n_faces, const float* gbuf, const int* pix, int n_pix, int samples, int s0,
+                                     int s_count, int seed, float eps, unsigned char* vis, hipStream_t stream) {
+    if (n_pix < 0 || n_faces <= 0 || samples < 2 || (samples & 1) || s0 < 0 || s_count < 0 || s0 + s_count > samples) return NU_ERR_ARG;
+    if (!bvh || !gbuf || !pix || !vis) return NU_ERR_ARG;
+    if (n_pix == 0 || s_count == 0) return NU_OK;
+    const int bpp = nu_cdiv(s_count, 16);
+    const long long blocks = (long long)n_pix * bpp;
+    if (blocks > 0x7fffffffLL) return NU_ERR_ARG;         // the caller chunks over pixels / samples
+    const NuBvhLayout L = nu_bvh_layout(n_faces);
+    NuRelightShadow src = {gbuf, pix, samples, s0, s_count, bpp, (unsigned)seed, eps, vis, 0};
+    // tmin = 0, tmax = 1e16 as every trace of this file; any hit: `found` is the closest-hit predicate (see the kernel)
+    hipLaunchKernelGGL((lbvh_trace_quad_kernel<NuRelightShadow, true>), dim3((unsigned)blocks), dim3(64), 0, stream, (const char*)bvh, L,
+                       src, 0.0f, 1e16f);
     return nu_launch_status();
 }
 

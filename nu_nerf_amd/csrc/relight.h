@@ -1,0 +1,151 @@
+// relight.h -- the device functions the relighting kernels share: the G-buffer row, the per-pixel sample sequence, the
+// shadow ray of a (pixel, sample), the lat-long environment lookup and the BRDF weight.  Included by lbvh.hip (the two traced passes
+// instantiate the traversal template there: the library is built without relocatable device code) and by relight.hip (resolve and the
+// debug entries).  ONE definition of each, compiled under the same flags with FMA contraction off, so that the ray the visibility pass
+// traces, the ray nu_relight_shadow_rays dumps and the direction nu_relight_resolve shades are the same bits.
+#pragma once
+#include "nu_common.h"
+
+#pragma clang fp contract(off)
+
+// G-buffer row of a pixel: NU_RL_ROW floats.  A miss pixel has face = NU_RL_MISS in the face array and an all-zero row.
+//   [0] t   [1..3] hit point   [4..6] geometric normal   [7..9] shading normal   [10..12] albedo   [13] metallic   [14] roughness
+//   [15..17] view vector (unit, surface -> camera)   [18] image index   [19] pixel index y * w + x of the full frame (both int bits)
+// Both normals are unit; the geometric one faces the viewer, the shading one lies on the geometric one's side.
+#define NU_RL_ROW 20
+#define NU_RL_MISS 10000000
+#define NU_RL_ALPHA_MIN 1e-3f        // GGX alpha = max(roughness^2, NU_RL_ALPHA_MIN)
+#define NU_RL_NOV_MIN 1e-4f          // N.V of the specular weight is clamped from below (silhouette pixels of a smooth-shaded mesh)
+
+static __device__ inline unsigned nu_rl_fmix32(unsigned h) {        // MurmurHash3's 32-bit finaliser
+    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+    return h;
+}
+
+// Sample s of S (S even) of a pixel: s < S/2 is index j = s of the S/2 cosine-weighted diffuse directions, s >= S/2 index j = s - S/2 of
+// the S/2 GGX half vectors.  Hammersley point (j / M, bit-reversed j), M = S/2, as 32-bit fixed point; Cranley-Patterson shift = two hash
+// words of (image, pixel, seed, lobe) added modulo 2^32; the two uniforms are the top 24 bits (exact in fp32).  Integer arithmetic up
+// to bits[0], bits[1].
+static __device__ inline void nu_relight_uniforms(int img, int pixel, unsigned seed, int S, int s, int& lobe, unsigned* bits) {
+    const int M = S >> 1;
+    lobe = s >= M ? 1 : 0;
+    const unsigned j = (unsigned)(s - lobe * M);
+    const unsigned x1 = (unsigned)(((unsigned long long)j << 32) / (unsigned long long)M);
+    const unsigned x2 = __brev(j);
+    unsigned a = nu_rl_fmix32((unsigned)img + 0x9E3779B9u);
+    a = nu_rl_fmix32(a ^ (unsigned)pixel);
+    a = nu_rl_fmix32(a ^ seed);
+    const unsigned h1 = nu_rl_fmix32(a + 2u * (unsigned)lobe + 1u);
+    const unsigned h2 = nu_rl_fmix32(h1 ^ 0x68E31DA4u);
+    bits[0] = (x1 + h1) >> 8;
+    bits[1] = (x2 + h2) >> 8;
+}
+
+// Orthonormal tangent frame of a unit normal (Duff et al. 2017, "Building an Orthonormal Basis, Revisited").
+static __device__ inline void nu_rl_frame(const float* n, float* t, float* b) {
+    const float sg = copysignf(1.0f, n[2]);
+    const float a = -1.0f / (sg + n[2]);
+    const float c = n[0] * n[1] * a;
+    t[0] = 1.0f + sg * n[0] * n[0] * a; t[1] = sg * c; t[2] = -sg * n[0];
+    b[0] = c; b[1] = sg + n[1] * n[1] * a; b[2] = -n[1];
+}
+
+// Light direction l (and, for the specular lobe, the half vector hv) of sample s of the pixel whose G-buffer row is g.  Returns true when
+// the sample is traced: l above the shading AND the geometric horizon (and V.H > 0 for a specular sample).  A sample that is not
+// traced counts as dark.
+static __device__ inline bool nu_relight_sample(const float* g, int S, int s, unsigned seed, int& lobe, float* l, float* hv,
+                                                unsigned* bits) {
+    nu_relight_uniforms(__float_as_int(g[18]), __float_as_int(g[19]), seed, S, s, lobe, bits);
+    const float u1 = (float)bits[0] * 5.9604644775390625e-08f, u2 = (float)bits[1] * 5.9604644775390625e-08f;   // 2^-24
+    const float* ng = g + 4;
+    const float* ns = g + 7;
+    const float* v = g + 15;
+    float t[3], b[3];
+    nu_rl_frame(ns, t, b);
+    float sp, cp;
+    sincosf(6.283185307179586f * u1, &sp, &cp);
+    float ct, st;
+    if (lobe == 0) {
+        ct = sqrtf(1.0f - u2);
+        st = sqrtf(u2);
+    } else {
+        const float a = fmaxf(g[14] * g[14], NU_RL_ALPHA_MIN);
+        const float om = 1.0f - u2;                              // exact: u2 is a multiple of 2^-24
+        const float den = om + (a * a) * u2;                     // cos^2 = (1 - u2) / (1 + (a^2 - 1) u2), written so that neither it
+        ct = sqrtf(om / den);                                    // nor sin^2 = 1 - cos^2 cancels
+        st = sqrtf((a * a) * u2 / den);
+    }
+    const float lx = st * cp, ly = st * sp;
+    float w[3];
+    for (int k = 0; k < 3; ++k) w[k] = (lx * t[k] + ly * b[k]) + ct * ns[k];
+    bool ok = true;
+    if (lobe == 0) {
+        for (int k = 0; k < 3; ++k) { l[k] = w[k]; hv[k] = 0.0f; }
+    } else {
+        const float voh = (v[0] * w[0] + v[1] * w[1]) + v[2] * w[2];
+        for (int k = 0; k < 3; ++k) { hv[k] = w[k]; l[k] = 2.0f * voh * w[k] - v[k]; }
+        ok = voh > 0.0f;
+    }
+    const float nsl = (ns[0] * l[0] + ns[1] * l[1]) + ns[2] * l[2];
+    const float ngl = (ng[0] * l[0] + ng[1] * l[1]) + ng[2] * l[2];
+    return ok && nsl > 0.0f && ngl > 0.0f;
+}
+
+// The shadow ray of (pixel row g, sample s): origin = hit point + eps * geometric normal, direction = the sample's l.
+static __device__ inline bool nu_relight_shadow_ray(const float* g, int S, int s, unsigned seed, float eps, float* o, float* d,
+                                                    unsigned* bits) {
+    int lobe;
+    float hv[3];
+    const bool traced = nu_relight_sample(g, S, s, seed, lobe, d, hv, bits);
+    for (int k = 0; k < 3; ++k) o[k] = g[1 + k] + eps * g[4 + k];
+    return traced;
+}
+
+// Lat-long environment, z up: column u = (1/2 - atan2(d.y, d.x) / 2 pi) * W, row v = atan2(hypot(d.x, d.y), d.z) / pi * H (row 0 = +z);
+// texel centres at half-integers, bilinear, wrapping in u and clamping in v.  env = RGBA fp32 [H, W]: a tap is one 16-byte load.
+static __device__ inline void nu_relight_env(const float4* __restrict__ env, int eh, int ew, const float* d, float* rgb) {
+    const float phi = atan2f(d[1], d[0]);
+    const float theta = atan2f(sqrtf(d[0] * d[0] + d[1] * d[1]), d[2]);
+    const float fx = (0.5f - phi * 0.15915494309189535f) * (float)ew - 0.5f;
+    const float fy = theta * 0.3183098861837907f * (float)eh - 0.5f;
+    const float x0 = floorf(fx), y0 = floorf(fy);
+    const float ax = fx - x0, ay = fy - y0;
+    int ix0 = (int)x0 % ew;
+    if (ix0 < 0) ix0 += ew;
+    const int ix1 = ix0 + 1 == ew ? 0 : ix0 + 1;
+    const int iy0 = min(max((int)y0, 0), eh - 1), iy1 = min(max((int)y0 + 1, 0), eh - 1);
+    const float4 t00 = env[(long long)iy0 * ew + ix0], t01 = env[(long long)iy0 * ew + ix1];
+    const float4 t10 = env[(long long)iy1 * ew + ix0], t11 = env[(long long)iy1 * ew + ix1];
+    const float bx = 1.0f - ax, by = 1.0f - ay;
+    rgb[0] = by * (bx * t00.x + ax * t01.x) + ay * (bx * t10.x + ax * t11.x);
+    rgb[1] = by * (bx * t00.y + ax * t01.y) + ay * (bx * t10.y + ax * t11.y);
+    rgb[2] = by * (bx * t00.z + ax * t01.z) + ay * (bx * t10.z + ax * t11.z);
+}
+
+// Separable Smith masking of GGX: G1(x) = 2 x / (x + sqrt(a^2 + (1 - a^2) x^2)).
+static __device__ inline float nu_rl_g1(float x, float a2) { return 2.0f * x / (x + sqrtf(a2 + (1.0f - a2) * x * x)); }
+
+// Weight of a traced sample (estimator / pdf, without visibility and radiance): diffuse (1 - metallic) * albedo for a cosine-weighted
+// direction; specular F G (V.H) / ((N.V) (N.H)) for an NDF-sampled half vector, F = Schlick with F0 = lerp(0.04, albedo, metallic).
+static __device__ inline void nu_relight_weight(const float* g, int lobe, const float* l, const float* hv, float* wgt) {
+    const float* ns = g + 7;
+    const float* v = g + 15;
+    const float metallic = g[13];
+    if (lobe == 0) {
+        for (int c = 0; c < 3; ++c) wgt[c] = (1.0f - metallic) * g[10 + c];
+        return;
+    }
+    const float a = fmaxf(g[14] * g[14], NU_RL_ALPHA_MIN), a2 = a * a;
+    const float nov = fmaxf((ns[0] * v[0] + ns[1] * v[1]) + ns[2] * v[2], NU_RL_NOV_MIN);
+    const float nol = (ns[0] * l[0] + ns[1] * l[1]) + ns[2] * l[2];
+    const float noh = (ns[0] * hv[0] + ns[1] * hv[1]) + ns[2] * hv[2];
+    const float voh = (v[0] * hv[0] + v[1] * hv[1]) + v[2] * hv[2];
+    const float G = nu_rl_g1(nol, a2) * nu_rl_g1(nov, a2);
+    const float m = 1.0f - fminf(voh, 1.0f);
+    const float fc = (m * m) * (m * m) * m;
+    const float k = G * voh / (nov * noh);
+    for (int c = 0; c < 3; ++c) {
+        const float f0 = 0.04f + (g[10 + c] - 0.04f) * metallic;
+        wgt[c] = (f0 + (1.0f - f0) * fc) * k;
+    }
+}

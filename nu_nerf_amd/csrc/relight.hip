@@ -1,0 +1,98 @@
+// relight.hip -- relighting of the baked mesh under a lat-long HDR environment (gfx950): the resolve pass and the debug entries.
+//
+// Replaces the reference's hand-off to Blender (relight.py -> blender_backend/relight_backend.py: Principled BSDF from vertex colours,
+// world environment texture, Cycles) with the project's own direct-light estimator, DESIGN.md 20.  Three passes per chunk of work:
+//   nu_relight_gbuffer     closest hit per pixel centre -> face id + G-buffer row            (lbvh.hip: instantiates the traversal)
+//   nu_relight_visibility  any-hit shadow ray per (hit pixel, sample), made in registers     (lbvh.hip)
+//   nu_relight_resolve     per pixel: the same directions again, environment tap, BRDF weight, summed in sample order   (here)
+// The sample sequence, the shadow ray, the environment lookup and the weight are relight.h, shared by all of them.  No allocation, no
+// synchronisation, every launch on the caller's stream; no atomics: a pixel is summed by one thread, sample after sample, into the
+// caller's accumulator, so the sum is the same bits however the pixels, images or sample ranges are chunked.
+#include "relight.h"
+
+__global__ __launch_bounds__(256) void relight_resolve_kernel(const float* __restrict__ gbuf, const int* __restrict__ pix, int n_pix, int S,
+                                                              int s0, int s_count, unsigned seed, const float4* __restrict__ env, int eh,
+                                                              int ew, const unsigned char* __restrict__ vis, float scale,
+                                                              float* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pix) return;
+    const long long row = pix[i];
+    float g[NU_RL_ROW];
+#pragma unroll
+    for (int k = 0; k < NU_RL_ROW; k += 4) {
+        const float4 q = *(const float4*)(gbuf + row * NU_RL_ROW + k);
+        g[k] = q.x; g[k + 1] = q.y; g[k + 2] = q.z; g[k + 3] = q.w;
+    }
+    float acc[3];
+    for (int c = 0; c < 3; ++c) acc[c] = out[row * 4 + c];
+    const unsigned char* lit = vis + (long long)i * s_count;
+    for (int c = 0; c < s_count; ++c) {
+        if (!lit[c]) continue;
+        int lobe;
+        float l[3], hv[3], rad[3], wgt[3];
+        unsigned bits[2];
+        nu_relight_sample(g, S, s0 + c, seed, lobe, l, hv, bits);
+        nu_relight_env(env, eh, ew, l, rad);
+        nu_relight_weight(g, lobe, l, hv, wgt);
+        for (int k = 0; k < 3; ++k) acc[k] = acc[k] + (wgt[k] * rad[k]) * scale;
+    }
+    for (int c = 0; c < 3; ++c) out[row * 4 + c] = acc[c];
+    out[row * 4 + 3] = 1.0f;
+}
+
+extern "C" int nu_relight_resolve(const float* gbuf, const int* pix, int n_pix, int samples, int s0, int s_count, int seed,
+                                  const float* env, int env_h, int env_w, const unsigned char* vis, float scale, float* out,
+                                  hipStream_t stream) {
+    if (n_pix < 0 || samples < 2 || (samples & 1) || s0 < 0 || s_count < 0 || s0 + s_count > samples || env_h <= 0 || env_w <= 0)
+        return NU_ERR_ARG;
+    if (!gbuf || !pix || !env || !vis || !out) return NU_ERR_ARG;
+    if (n_pix == 0 || s_count == 0) return NU_OK;
+    hipLaunchKernelGGL(relight_resolve_kernel, dim3(nu_cdiv(n_pix, 256)), dim3(256), 0, stream, gbuf, pix, n_pix, samples, s0, s_count,
+                       (unsigned)seed, (const float4*)env, env_h, env_w, vis, scale, out);
+    return nu_launch_status();
+}
+
+// exactly the rays nu_relight_visibility makes (the same device function), written out: rays [n_pix * s_count, 6]; bits (optional)
+// [n_pix * s_count, 3] = the two 24-bit sample integers and 1 where the ray is traced
+__global__ __launch_bounds__(256) void relight_shadow_rays_kernel(const float* __restrict__ gbuf, const int* __restrict__ pix, int n_pix,
+                                                                  int S, int s0, int s_count, unsigned seed, float eps,
+                                                                  float* __restrict__ rays, int* __restrict__ bits_out) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= (long long)n_pix * s_count) return;
+    const int i = (int)(r / s_count), c = (int)(r - (long long)i * s_count);
+    float o[3], d[3];
+    unsigned bits[2];
+    const bool traced = nu_relight_shadow_ray(gbuf + (long long)pix[i] * NU_RL_ROW, S, s0 + c, seed, eps, o, d, bits);
+    for (int k = 0; k < 3; ++k) { rays[r * 6 + k] = o[k]; rays[r * 6 + 3 + k] = d[k]; }
+    if (bits_out) { bits_out[r * 3] = (int)bits[0]; bits_out[r * 3 + 1] = (int)bits[1]; bits_out[r * 3 + 2] = traced ? 1 : 0; }
+}
+
+extern "C" int nu_relight_shadow_rays(const float* gbuf, const int* pix, int n_pix, int samples, int s0, int s_count, int seed, float eps,
+                                      float* rays, int* bits, hipStream_t stream) {
+    if (n_pix < 0 || samples < 2 || (samples & 1) || s0 < 0 || s_count < 0 || s0 + s_count > samples) return NU_ERR_ARG;
+    if (!gbuf || !pix || !rays) return NU_ERR_ARG;
+    const long long N = (long long)n_pix * s_count;
+    if (N == 0) return NU_OK;
+    if (nu_cdivl(N, 256) > 0x7fffffffLL) return NU_ERR_ARG;
+    hipLaunchKernelGGL(relight_shadow_rays_kernel, dim3((unsigned)nu_cdivl(N, 256)), dim3(256), 0, stream, gbuf, pix, n_pix, samples, s0,
+                       s_count, (unsigned)seed, eps, rays, bits);
+    return nu_launch_status();
+}
+
+__global__ __launch_bounds__(256) void relight_env_lookup_kernel(const float4* __restrict__ env, int eh, int ew,
+                                                                 const float* __restrict__ dirs, int N, float* __restrict__ out) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= N) return;
+    const float d[3] = {dirs[r * 3LL], dirs[r * 3LL + 1], dirs[r * 3LL + 2]};
+    float rgb[3];
+    nu_relight_env(env, eh, ew, d, rgb);
+    for (int k = 0; k < 3; ++k) out[r * 3LL + k] = rgb[k];
+}
+
+extern "C" int nu_relight_env_lookup(const float* env, int env_h, int env_w, const float* dirs, int N, float* out, hipStream_t stream) {
+    if (N < 0 || env_h <= 0 || env_w <= 0 || !env || (N > 0 && (!dirs || !out))) return NU_ERR_ARG;
+    if (N == 0) return NU_OK;
+    hipLaunchKernelGGL(relight_env_lookup_kernel, dim3(nu_cdiv(N, 256)), dim3(256), 0, stream, (const float4*)env, env_h, env_w, dirs, N,
+                       out);
+    return nu_launch_status();
+}

@@ -1,0 +1,380 @@
+"""python -m nu_nerf_amd.relight --mesh PLY --material DIR --hdr FILE --name NAME [--trans] [--num 360 --width 800 --height 800
+--samples 1024 --cam_dist 3.0 --azimuth 0 --elevation 45]
+
+relight.py + blender_backend/relight_backend.py on the GPU: the extracted mesh, the per-vertex DIR/metallic.npy, roughness.npy and
+albedo.npy that extract_materials writes and a lat-long HDR environment map are rendered from the reference's camera orbit
+(generate_relghting_poses) into data/relight/NAME/{k}.png, RGBA with alpha 0 off the object (film_transparent); frames that exist are
+skipped (relight_backend.py:82).  Blender is not involved: primary visibility, a G-buffer and `samples` shadow rays per hit pixel are
+traced on the HIP LBVH (nu_relight_gbuffer, nu_relight_visibility) and shaded by nu_relight_resolve with the material model the
+networks were trained under.  DESIGN.md 20 defines the light transport and lists what is not Cycles; nothing here is pinned
+against Blender output.
+
+--hdr takes a Radiance .hdr (RGBE, flat or run-length scanlines) or a .npy float [H,W,3]; the map is z up in the mesh's frame.
+--focal_mm / --sensor_mm: Blender's default camera (50 mm on a 36 mm sensor fitted to the larger image side).  --seed, --chunk
+(samples per pass; bounds device memory) and --output (default data/relight/NAME) are this project's own.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROW = 20                        # floats per G-buffer row (csrc/relight.h)
+MISS = 10000000
+ORIGIN_EPS = 1e-4               # shadow-ray origin = hit point + ORIGIN_EPS * viewer-facing geometric normal (scenes live in the unit sphere)
+VIS_BYTES = 256 << 20           # the visibility bytes of one pass never exceed this
+R_BLENDER = np.array([[1.0, 0.0, 0.0], [0.0, 0.0, -1.0], [0.0, 1.0, 0.0]])     # x_blender = R_BLENDER @ x_wrd (set_camera_by_pose)
+TRANS = R_BLENDER               # --trans: the mesh turned +90 degrees about x (relight_backend.py:46-48) -- the same matrix
+
+
+# ---- cameras ---------------------------------------------------------------------------------------------------------------------------
+def relighting_poses(num, azimuth, elevation, dist):
+    """blender_utils.generate_relghting_poses: [num,3,4] float64 world -> camera [R|t] (x right, y down, z forward), t = (0, 0, dist);
+    azimuths = azimuth + linspace(-90, 90, num) degrees at a fixed elevation, looking at the origin with z up, the rotation composed
+    with R_trans (x_norm = R_trans x_wrd)."""
+    az = np.deg2rad(azimuth) + np.linspace(-np.pi / 2, np.pi / 2, num)
+    el = np.ones_like(az) * np.deg2rad(elevation)
+    pts = np.stack([np.cos(az) * np.cos(el), np.sin(az) * np.cos(el), np.sin(el)], -1)
+    up = np.array([0.0, 0.0, 1.0])
+    z = -pts / np.linalg.norm(pts, 2, 1, keepdims=True)
+    y = -(up[None, :] - np.sum(z * up[None, :], 1, keepdims=True) * z)
+    y = y / np.linalg.norm(y, 2, 1, keepdims=True)
+    x = np.cross(y, z)
+    rot = np.stack([x, y, z], 1) @ R_BLENDER[None]
+    t = np.repeat(np.array([0.0, 0.0, dist])[None, :, None], num, 0)
+    return np.concatenate([rot, t], -1)
+
+
+def camera_in_mesh_frame(pose):
+    """The frame change of set_camera_by_pose without its final Blender-camera axis flip: pose [...,3,4] (x_cam = R x_wrd + t) ->
+    [R R_blender^T | t], the world -> camera transform in the frame the mesh is imported into (x_blender = R_blender x_wrd).  With the
+    poses of relighting_poses R_trans and R_blender cancel: the result is the plain z-up look-at orbit."""
+    pose = np.asarray(pose, np.float64)
+    return np.concatenate([pose[..., :3] @ R_BLENDER.T, pose[..., 3:]], -1)
+
+
+def intrinsics(h, w, focal_mm=50.0, sensor_mm=36.0):
+    """K [3,3] float64 of Blender's default camera: fx = fy = focal / sensor * max(w, h), centre (w / 2, h / 2)."""
+    f = focal_mm / sensor_mm * max(w, h)
+    return np.array([[f, 0.0, w / 2.0], [0.0, f, h / 2.0], [0.0, 0.0, 1.0]])
+
+
+# ---- environment maps --------------------------------------------------------------------------------------------------------------
+def read_hdr(path):
+    """float32 [H,W,3] from a Radiance RGBE file (flat or new run-length scanlines, `-Y H +X W`) or a .npy float [H,W,3].
+    An RGBE pixel (r, g, b, e) is (r, g, b) * 2^(e - 136), and 0 when e = 0: exact in fp32."""
+    path = str(path)
+    if path.lower().endswith('.npy'):
+        a = np.load(path)
+        if a.ndim != 3 or a.shape[2] != 3 or not np.issubdtype(a.dtype, np.floating):
+            raise ValueError(f"{path}: expected a float array [H,W,3], got {a.dtype} {a.shape}")
+        return np.ascontiguousarray(a, np.float32)
+    with open(path, 'rb') as fh:
+        data = fh.read()
+    pos, fmt, first = 0, None, True
+    while True:
+        end = data.find(b'\n', pos)
+        if end < 0:
+            raise ValueError(f"{path}: the header does not end")
+        line = data[pos:end].strip()
+        pos = end + 1
+        if first:
+            if not line.startswith(b'#?'):
+                raise ValueError(f"{path}: not a Radiance file (no #? signature)")
+            first = False
+            continue
+        if not line:
+            break
+        if line.startswith(b'FORMAT='):
+            fmt = line[7:].strip()
+    if fmt != b'32-bit_rle_rgbe':
+        raise ValueError(f"{path}: FORMAT is {fmt!r}, only 32-bit_rle_rgbe is read")
+    end = data.find(b'\n', pos)
+    tok = data[pos:end].split() if end >= 0 else []
+    if len(tok) != 4 or tok[0] != b'-Y' or tok[2] != b'+X' or not (tok[1].isdigit() and tok[3].isdigit()):
+        raise ValueError(f"{path}: resolution line {data[pos:max(end, pos)][:40]!r} is not `-Y H +X W`")
+    h, w = int(tok[1]), int(tok[3])
+    if h <= 0 or w <= 0:
+        raise ValueError(f"{path}: empty image {h} x {w}")
+    pos = end + 1
+    buf = np.frombuffer(data, np.uint8)
+    rgbe = np.empty((h, w, 4), np.uint8)
+    for y in range(h):
+        if pos + 4 > len(buf):
+            raise ValueError(f"{path}: the pixel data ends in scanline {y}")
+        if 8 <= w <= 0x7fff and buf[pos] == 2 and buf[pos + 1] == 2 and (int(buf[pos + 2]) << 8 | int(buf[pos + 3])) == w:
+            pos += 4
+            for c in range(4):
+                x = 0
+                while x < w:
+                    if pos >= len(buf):
+                        raise ValueError(f"{path}: the pixel data ends in scanline {y}")
+                    n = int(buf[pos])
+                    pos += 1
+                    if n > 128:
+                        n -= 128
+                        if n == 0 or x + n > w or pos >= len(buf):
+                            raise ValueError(f"{path}: bad run in scanline {y}")
+                        rgbe[y, x:x + n, c] = buf[pos]
+                        pos += 1
+                    else:
+                        if n == 0 or x + n > w or pos + n > len(buf):
+                            raise ValueError(f"{path}: bad literal in scanline {y}")
+                        rgbe[y, x:x + n, c] = buf[pos:pos + n]
+                        pos += n
+                    x += n
+        else:
+            if pos + 4 * w > len(buf):
+                raise ValueError(f"{path}: the pixel data ends in scanline {y}")
+            rgbe[y] = buf[pos:pos + 4 * w].reshape(w, 4)
+            pos += 4 * w
+    e = rgbe[..., 3].astype(np.int32)
+    out = np.ldexp(rgbe[..., :3].astype(np.float32), (e - 136)[..., None]).astype(np.float32)
+    out[e == 0] = 0.0
+    return out
+
+
+def pack_env(env):
+    """float32 [H,W,4] RGBA (A = 1) from [H,W,3]: one 16-byte load per tap on the device."""
+    env = np.asarray(env, np.float32)
+    if env.ndim != 3 or env.shape[2] != 3 or env.shape[0] < 1 or env.shape[1] < 1:
+        raise ValueError(f"environment map must be [H,W,3], got {env.shape}")
+    if not np.isfinite(env).all():
+        raise ValueError("environment map has non-finite values")
+    return np.ascontiguousarray(np.concatenate([env, np.ones_like(env[..., :1])], -1))
+
+
+# ---- device passes -----------------------------------------------------------------------------------------------------------------------
+class Scene:
+    """Mesh + LBVH + what the G-buffer pass interpolates: unit vertex normals [V,3] and materials [V,5] = albedo, metallic, roughness.
+    materials: a dict with 'albedo' [V,3], 'metallic' [V,1], 'roughness' [V,1] (the arrays extract_materials writes) or one [V,5]."""
+
+    def __init__(self, V, F, materials, device=None):
+        import torch
+        from .lbvh import LBVH, vertex_normals_and_curvature
+        dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        V = torch.as_tensor(np.asarray(V) if not torch.is_tensor(V) else V).to(torch.float32)
+        F = torch.as_tensor(np.asarray(F) if not torch.is_tensor(F) else F).to(torch.int32)
+        if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
+            raise ValueError(f"mesh must be V [Nv,3], F [Nf,3], got {tuple(V.shape)} {tuple(F.shape)}")
+        if F.numel() and (int(F.min()) < 0 or int(F.max()) >= V.shape[0]):
+            raise ValueError("face index out of range")
+        if isinstance(materials, dict):
+            m = np.concatenate([np.asarray(materials['albedo'], np.float32).reshape(-1, 3),
+                                np.asarray(materials['metallic'], np.float32).reshape(-1, 1),
+                                np.asarray(materials['roughness'], np.float32).reshape(-1, 1)], 1)
+        else:
+            m = np.asarray(materials.cpu() if torch.is_tensor(materials) else materials, np.float32)
+        if m.shape != (V.shape[0], 5):
+            raise ValueError(f"materials must give 5 values for each of the {V.shape[0]} vertices, got {m.shape}")
+        self.V, self.F = V.to(dev).contiguous(), F.to(dev).contiguous()
+        self.bvh = LBVH(self.V, self.F)
+        self.normals = vertex_normals_and_curvature(V, F)[0].to(dev).contiguous()
+        self.materials = torch.from_numpy(np.ascontiguousarray(m)).to(dev)
+        self.device = dev
+
+
+def gbuffer(scene, cams, h, w, img0=0, y0=0, rows=None):
+    """face int32 [n, rows, w], gbuf float32 [n, rows, w, ROW] of rows [y0, y0 + rows) of the images of cams [n,21]."""
+    import torch
+    from . import _lib as L
+    rows = h - y0 if rows is None else rows
+    n = int(cams.shape[0])
+    face = torch.empty(n, rows, w, dtype=torch.int32, device=scene.device)
+    gbuf = torch.empty(n, rows, w, ROW, dtype=torch.float32, device=scene.device)
+    L.load().nu_relight_gbuffer(L.ptr(scene.bvh.buf), scene.bvh.n_faces, L.ptr(scene.V), L.ptr(scene.F), L.ptr(scene.normals),
+                                L.ptr(scene.materials), L.ptr(cams), n, int(img0), int(h), int(w), int(y0), int(rows), L.ptr(face),
+                                L.ptr(gbuf), L.stream())
+    return face, gbuf
+
+
+def hit_pixels(face):
+    """int32 indices of the G-buffer rows that hold a hit (one device -> host read: the count)."""
+    import torch
+    return (face.reshape(-1) != MISS).nonzero().flatten().to(torch.int32)
+
+
+def visibility(scene, gbuf, pix, samples, s0, s_count, seed, eps=ORIGIN_EPS):
+    """uint8 [n_pix, s_count]: 1 where sample s0 + c of pixel pix[i] sees the environment."""
+    import torch
+    from . import _lib as L
+    vis = torch.empty(int(pix.shape[0]), int(s_count), dtype=torch.uint8, device=gbuf.device)
+    L.load().nu_relight_visibility(L.ptr(scene.bvh.buf), scene.bvh.n_faces, L.ptr(gbuf), L.ptr(pix), int(pix.shape[0]), int(samples),
+                                   int(s0), int(s_count), _seed(seed), float(eps), L.ptr(vis), L.stream())
+    return vis
+
+
+def shadow_rays(gbuf, pix, samples, s0, s_count, seed, eps=ORIGIN_EPS):
+    """(rays float32 [n_pix * s_count, 6], bits int32 [n_pix * s_count, 3]): the rays visibility() traces, the two 24-bit sample
+    integers behind each and 1 where it is traced (tests)."""
+    import torch
+    from . import _lib as L
+    N = int(pix.shape[0]) * int(s_count)
+    rays = torch.empty(N, 6, dtype=torch.float32, device=gbuf.device)
+    bits = torch.empty(N, 3, dtype=torch.int32, device=gbuf.device)
+    L.load().nu_relight_shadow_rays(L.ptr(gbuf), L.ptr(pix), int(pix.shape[0]), int(samples), int(s0), int(s_count), _seed(seed),
+                                    float(eps), L.ptr(rays), L.ptr(bits), L.stream())
+    return rays, bits
+
+
+def resolve(gbuf, pix, samples, s0, s_count, seed, env, vis, out):
+    """out [rows of gbuf, 4] += the shaded samples [s0, s0 + s_count) of the listed pixels (env: packed RGBA on the device)."""
+    from . import _lib as L
+    L.load().nu_relight_resolve(L.ptr(gbuf), L.ptr(pix), int(pix.shape[0]), int(samples), int(s0), int(s_count), _seed(seed), L.ptr(env),
+                                int(env.shape[0]), int(env.shape[1]), L.ptr(vis), 2.0 / samples, L.ptr(out), L.stream())
+    return out
+
+
+def env_lookup(env, dirs):
+    """Bilinear lat-long lookup of the packed environment at dirs [N,3] -> [N,3] (tests)."""
+    import torch
+    from . import _lib as L
+    dirs = dirs.to(torch.float32).contiguous()
+    out = torch.empty(dirs.shape[0], 3, dtype=torch.float32, device=dirs.device)
+    L.load().nu_relight_env_lookup(L.ptr(env), int(env.shape[0]), int(env.shape[1]), L.ptr(dirs), int(dirs.shape[0]), L.ptr(out), L.stream())
+    return out
+
+
+def _seed(seed):
+    """The seed as the C int the ABI takes (its 32 bits are what the hash reads)."""
+    seed = int(seed) & 0xffffffff
+    return seed - (1 << 32) if seed >= 1 << 31 else seed
+
+
+def _scene(V, F=None, materials=None):
+    return V if isinstance(V, Scene) else Scene(V, F, materials)
+
+
+def relight_linear(V, F, materials, env, poses, h, w, samples, seed=0, chunk=256, rows=None, images=1, K=None, img0=0,
+                   eps=ORIGIN_EPS):
+    """Linear radiance float32 [n,h,w,4] (RGB, alpha 1 on hit pixels and 0 elsewhere) on the device.  poses [n,3,4]: world -> camera in
+    the mesh's frame (camera_in_mesh_frame of relighting_poses); K: [3,3] (default intrinsics(h, w)); env [H,W,3]; V may be a Scene.
+    Image i is sampled as image img0 + i.  Work is done `images` images x `rows` image rows x `chunk` samples at a time; the result
+    does not depend on any of the three, bit for bit.  Device memory besides the mesh, the environment and the result: 100 bytes per
+    pixel of a piece (G-buffer row, face id, hit list) plus at most VIS_BYTES of visibility bytes -- independent of `samples`."""
+    import torch
+    from .mask_render import _cams
+    samples, chunk = int(samples), int(chunk)
+    if samples < 2 or samples % 2:
+        raise ValueError(f"samples must be even and >= 2, got {samples}")
+    if chunk < 1 or images < 1 or (rows is not None and rows < 1):
+        raise ValueError("chunk, rows and images must be >= 1")
+    scene = _scene(V, F, materials)
+    dev = scene.device
+    poses = np.asarray(poses.cpu() if torch.is_tensor(poses) else poses, np.float64).reshape(-1, 3, 4)
+    K = intrinsics(h, w) if K is None else np.asarray(K, np.float64)
+    cams = _cams(K.astype(np.float32), poses.astype(np.float32), dev)
+    envd = torch.from_numpy(pack_env(env)).to(dev)
+    n, rows = int(cams.shape[0]), int(rows or h)
+    out = torch.zeros(n, h, w, 4, dtype=torch.float32, device=dev)
+    for i0 in range(0, n, images):
+        ni = min(images, n - i0)
+        for y0 in range(0, h, rows):
+            nr = min(rows, h - y0)
+            face, gbuf = gbuffer(scene, cams[i0:i0 + ni], h, w, img0 + i0, y0, nr)
+            pix_all = hit_pixels(face)
+            piece = torch.zeros(ni * nr * w, 4, dtype=torch.float32, device=dev)
+            per = max(1, min(VIS_BYTES // min(chunk, samples), (2 ** 31 - 1) // ((min(chunk, samples) + 15) // 16)))
+            for p0 in range(0, int(pix_all.shape[0]), per):
+                pix = pix_all[p0:p0 + per].contiguous()
+                for s0 in range(0, samples, chunk):
+                    sc = min(chunk, samples - s0)
+                    vis = visibility(scene, gbuf, pix, samples, s0, sc, seed, eps)
+                    resolve(gbuf, pix, samples, s0, sc, seed, envd, vis, piece)
+            out[i0:i0 + ni, y0:y0 + nr] = piece.reshape(ni, nr, w, 4)
+    return out
+
+
+def to_srgb8(linear):
+    """uint8 [..., 4] from linear RGBA: RGB through the project's linear_to_srgb, clipped to [0, 1], rounded to 8 bits; alpha 255 / 0."""
+    import torch
+    from .torch_glue import linear_to_srgb
+    rgb = linear_to_srgb(linear[..., :3]).clamp(0.0, 1.0)
+    return torch.cat([torch.floor(rgb * 255.0 + 0.5), linear[..., 3:] * 255.0], -1).to(torch.uint8)
+
+
+def relight(V, F, materials, env, poses, h, w, samples, seed=0, chunk=256, **kw):
+    """uint8 [n,h,w,4] sRGB + alpha of relight_linear (same arguments)."""
+    return to_srgb8(relight_linear(V, F, materials, env, poses, h, w, samples, seed, chunk, **kw))
+
+
+def write_png(path, rgba):
+    """RGBA uint8 [h,w,4] as a PNG (Pillow)."""
+    from .mask_render import _pillow
+    a = np.ascontiguousarray(rgba.cpu().numpy() if hasattr(rgba, 'cpu') else rgba, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"write_png: expected [h,w,4], got {a.shape}")
+    _pillow().fromarray(a, 'RGBA').save(path)
+    return path
+
+
+# ---- the command ---------------------------------------------------------------------------------------------------------------------
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m nu_nerf_amd.relight", description=__doc__.split("\n\n")[1])
+    ap.add_argument('--mesh', type=str, required=True, help="triangle mesh (PLY)")
+    ap.add_argument('--material', type=str, required=True, help="directory with metallic.npy, roughness.npy, albedo.npy")
+    ap.add_argument('--hdr', type=str, required=True, help="environment map: Radiance .hdr or .npy float [H,W,3]")
+    ap.add_argument('--name', type=str, required=True, help="frames go to data/relight/NAME")
+    ap.add_argument('--trans', action='store_true', default=False, help="turn the mesh +90 degrees about x")
+    ap.add_argument('--output', type=str, default=None, help="output directory (default data/relight/NAME)")
+    ap.add_argument('--width', type=int, default=800)
+    ap.add_argument('--height', type=int, default=800)
+    ap.add_argument('--samples', type=int, default=1024)
+    ap.add_argument('--cam_dist', type=float, default=3.0)
+    ap.add_argument('--num', type=int, default=360)
+    ap.add_argument('--azimuth', type=float, default=0.0)
+    ap.add_argument('--elevation', type=float, default=45.0)
+    ap.add_argument('--focal_mm', type=float, default=50.0)
+    ap.add_argument('--sensor_mm', type=float, default=36.0)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--chunk', type=int, default=256, help="samples per pass")
+    flags = ap.parse_args(argv)
+    if flags.samples < 2 or flags.samples % 2:
+        ap.error("--samples must be even and >= 2")
+    if flags.num < 1 or flags.width < 1 or flags.height < 1 or flags.chunk < 1:
+        ap.error("--num, --width, --height and --chunk must be >= 1")
+    return flags
+
+
+def output_dir(flags):
+    return flags.output or os.path.join('data', 'relight', flags.name)
+
+
+def frame_path(out, k):
+    return os.path.join(out, f'{k}.png')
+
+
+def frames_to_render(out, num):
+    """The frame numbers without a file yet (relight_backend.py:82)."""
+    return [k for k in range(num) if not os.path.exists(frame_path(out, k))]
+
+
+def load_materials(directory):
+    return {k: np.load(os.path.join(directory, k + '.npy')) for k in ('metallic', 'roughness', 'albedo')}
+
+
+def main(argv=None):
+    flags = parse_args(argv)
+    out = output_dir(flags)
+    os.makedirs(out, exist_ok=True)
+    todo = frames_to_render(out, flags.num)
+    if not todo:
+        print(f'{out}: all {flags.num} frames exist')
+        return out
+    from . import mesh as M
+    V, F = M.read_ply(flags.mesh)
+    if flags.trans:
+        V = (np.asarray(V, np.float64) @ TRANS.T).astype(np.float32)
+    scene = Scene(V, F, load_materials(flags.material))
+    env = read_hdr(flags.hdr)
+    poses = camera_in_mesh_frame(relighting_poses(flags.num, flags.azimuth, flags.elevation, flags.cam_dist))
+    K = intrinsics(flags.height, flags.width, flags.focal_mm, flags.sensor_mm)
+    for k in todo:
+        img = relight(scene, None, None, env, poses[k:k + 1], flags.height, flags.width, flags.samples, flags.seed, flags.chunk, K=K, img0=k)
+        write_png(frame_path(out, k), img[0])
+    print(f'wrote {len(todo)} frames to {out} ({flags.num - len(todo)} existed)')
+    return out
+
+
+if __name__ == "__main__":
+    sys.exit(0 if main() else 1)
