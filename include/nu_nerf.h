@@ -379,6 +379,63 @@ int nu_relight_shadow_rays(const float* gbuf, const int* pix, int n_pix, int sam
 int nu_relight_env_lookup(const float* env, int env_h, int env_w, const float* dirs, int N, float* out, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Relighting of the NESTED object (the project's own transport, pinned against no other renderer): a
+ * transparent outer shell (tree, V_o, F_o, unit vertex normals, index of refraction ior [V_o] >= 1) around an opaque inner mesh
+ * (tree, V_i, F_i, unit vertex normals, materials_i [V_i,5]).  The outer G-buffer comes from nu_relight_gbuffer run on the outer mesh
+ * with ior - 1 in column 0 of its materials, so that 1 + row[10] is the interpolated index at the primary hit (the excess over 1 is
+ * what is interpolated everywhere: a constant index stays that index bit for bit, and an index-matched shell, ior = 1, is exactly absent).
+ *   nu_relight_nested_chain    pix [n_pix] = HIT rows of the outer G-buffer.  Per listed pixel, in one launch: the entry interface
+ *                              event, the reflection ray (any hit, outer), up to max_segments interior segments (closest hit against
+ *                              the inner and the outer tree; inner first when t_inner <= t_outer; total internal reflection goes on),
+ *                              the exit ray (any hit, outer).  kind [n_pix] = NU_RLN_DARK / _INNER / _EXIT; chain [n_pix, 12] =
+ *                              T, exit direction [3], exit visibility, reflection direction [3], F_entry, reflection visibility,
+ *                              segments walked (int bits), 0; inner_rows [n_pix, 20] = the G-buffer row of the inner hit (zero for
+ *                              the other kinds; image and pixel index copied from the outer row).
+ *   nu_relight_nested_light    sel [n_sel] = indices of INNER pixels into inner_rows; samples [s0, s0 + s_count) of `samples`: per
+ *                              (pixel, sample) the light path -- any hit against the inner tree from x + eps n_g, closest hit against
+ *                              the outer tree along the same ray, interface event going out, any hit against the outer tree along the
+ *                              exit ray -- walked back to back, no ray stored.  rec [n_sel, s_count, 4] = (exit direction,
+ *                              1 - F_exit), all zero for a dark or untraced sample.  n_sel * ceil(s_count / 16) stays below 2^31.
+ *   nu_relight_nested_resolve  out [rows of the outer G-buffer, 4] += per listed pixel sel[i] (indices into kind / chain / inner_rows;
+ *                              opix [n_pix] = the row each writes), in sample order, scale * T * weight * (1 - F_exit) * env(exit
+ *                              direction) of the records rec [n_sel, s_count, 4]; when last != 0 also the reflection term and, for
+ *                              an exit pixel, T * env(exit direction) * visibility.  alpha = 1.  No atomics: same bits however the
+ *                              pixels, images and sample ranges are chunked.  s_count may be 0 (rec may then be NULL).
+ *   nu_relight_nested_chain_dump / _light_dump   the same kernels, also writing what they traced (tests):
+ *                              seg [n_pix, max_segments, 16] = per walked segment ray o [3], d [3], then as int bits the mesh that ended
+ *                              it (0 none, 1 inner, 2 outer) and its face id, t, then (found, face id, t) of the inner and of the
+ *                              outer walk, 1; aux [n_pix, 2, 8] = reflection ray and exit ray: o [3], d [3], traced, found.
+ *                              dump [n_sel * s_count, 20] = ray o [3], d [3], traced, inner found, outer found, outer face (int bits),
+ *                              outer t, refracted, exit ray o [3], d [3], exit found, 1 - F_exit.
+ * --------------------------------------------------------------------------------------------------------- */
+#define NU_RLN_MAX_SEGMENTS 4
+#define NU_RLN_DARK 0
+#define NU_RLN_INNER 1
+#define NU_RLN_EXIT 2
+#define NU_RLN_CHAIN 12
+#define NU_RLN_SEG 16
+#define NU_RLN_LIGHT_DUMP 20
+int nu_relight_nested_chain(const void* bvh_o, int n_faces_o, const float* V_o, const int* F_o, const float* vnormals_o, const float* ior,
+    const void* bvh_i, int n_faces_i, const float* V_i, const int* F_i, const float* vnormals_i, const float* materials_i,
+    const float* gbuf, const int* pix, int n_pix, float eps, int max_segments, int* kind,
+                            float* chain, float* inner_rows, hipStream_t stream);
+int nu_relight_nested_chain_dump(const void* bvh_o, int n_faces_o, const float* V_o, const int* F_o, const float* vnormals_o, const float* ior,
+    const void* bvh_i, int n_faces_i, const float* V_i, const int* F_i, const float* vnormals_i, const float* materials_i,
+    const float* gbuf, const int* pix, int n_pix, float eps, int max_segments, int* kind,
+                                 float* chain, float* inner_rows, float* seg, float* aux, hipStream_t stream);
+int nu_relight_nested_light(const void* bvh_o, int n_faces_o, const float* V_o, const int* F_o, const float* vnormals_o, const float* ior,
+    const void* bvh_i, int n_faces_i, const float* V_i, const int* F_i, const float* vnormals_i, const float* materials_i,
+    const float* inner_rows, const int* sel, int n_sel, int samples, int s0, int s_count,
+                            int seed, float eps, float* rec, hipStream_t stream);
+int nu_relight_nested_light_dump(const void* bvh_o, int n_faces_o, const float* V_o, const int* F_o, const float* vnormals_o, const float* ior,
+    const void* bvh_i, int n_faces_i, const float* V_i, const int* F_i, const float* vnormals_i, const float* materials_i,
+    const float* inner_rows, const int* sel, int n_sel, int samples, int s0, int s_count,
+                                 int seed, float eps, float* rec, float* dump, hipStream_t stream);
+int nu_relight_nested_resolve(const float* inner_rows, const float* chain, const int* kind, const int* opix, const int* sel, int n_sel,
+                              int samples, int s0, int s_count, int seed, const float* env, int env_h, int env_w, const float* rec,
+                              float scale, int last, float* out, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Validation metrics (network/metrics.py): PSNR and SSIM of uint8 images [n, h, w, c], channel-interleaved, c in {1, 3}.
  * Pointers need no alignment.  DESIGN.md section 18 has the exactness argument and the reduction order.
  * --------------------------------------------------------------------------------------------------------- */

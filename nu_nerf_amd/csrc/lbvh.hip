@@ -437,6 +437,10 @@ struct NuPinholeMask {                     // every pixel of n images -> uint8 0
     __device__ __forceinline__ void end(int found, int, float) { out[p] = found ? 255 : 0; }
 };
 
+// (nu_walk_quad further down is this walk a second time, as a device function for the kernels that trace several dependent rays per
+// quad: a change to the walk is made in both.  Calling it from here, with ANY_HIT passed as a constant, was tried and changes the
+// compiler's figures of all four instantiations below -- VGPR 66 / 63 / 68 / 61 -> 72 / 59 / 72 / 59, SGPR 42 / 46 / 58 / 47 ->
+// 42 / 44 / 52 / 41 (scripts/kernel_regs.py; LDS and scratch stay) -- so they keep their own code)
 // ANY_HIT = false: closest hit (nu_lbvh_trace).  ANY_HIT = true: the ray ends as soon as a lane of its quad accepts a triangle; until
 // then the running best is tmax, so the walk is step for step the closest-hit walk and `found` is the same predicate (the boxes are
 // padded so that no accepted triangle is ever culled) -- only the (t, face id) of an any-hit are not the closest ones.
@@ -732,6 +736,357 @@ extern "C" int nu_relight_visibility(const void* bvh, int n_faces, const float* 
     hipLaunchKernelGGL((lbvh_trace_quad_kernel<NuRelightShadow, true>), dim3((unsigned)blocks), dim3(64), 0, stream, (const char*)bvh, L,
                        src, 0.0f, 1e16f);
     return nu_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------------
+// relighting of the nested object: several DEPENDENT walks per quad, through two trees, in one launch.
+//
+// nu_walk_quad is the walk of lbvh_trace_quad_kernel written a second time as a device function (that kernel is left as it is: its
+// instantiations keep their register figures and their bits): the same records, the same box and triangle tests in the same order,
+// the same ordering inside the quad, the same stack discipline -- so (found, face id, t) of a closest-hit walk and `found` of an
+// any-hit walk are those of nu_lbvh_trace on the same ray, bit for bit.  any_hit is a run-time flag here, and the walk may be
+// called again and again by a quad: the stack column of the quad is empty whenever a walk ends (an any-hit walk that leaves early
+// simply starts the next one at sp = 0).  The kernels below call it from ONE site inside a per-quad state machine, so the quads of a
+// wave that are at different steps of their paths still share the loop.
+// ------------------------------------------------------------------------------------------------
+static __device__ __forceinline__ void nu_walk_quad(int (*stack)[16], int q, int sub, const char* __restrict__ buf, const NuBvhLayout L,
+                                                    const float* o, const float* d, float tmin, float tmax, bool any_hit, int& found,
+                                                    int& best_id, float& best_t) {
+    const NuBvhHeader* h = (const NuBvhHeader*)(buf + L.header);
+    const NuBvhWideEntry* wide = (const NuBvhWideEntry*)(buf + L.wide);
+    const float* tris = (const float*)(buf + L.tris);
+    const int* ids = (const int*)(buf + L.ids);
+    const int n = h->n_faces;
+    float invd[3];
+    for (int k = 0; k < 3; ++k) invd[k] = 1.0f / d[k];
+    best_t = tmax;
+    best_id = NU_MISS_INDEX;
+    found = 0;
+    auto merge = [&](int cf, float ct, int ci) {
+#define NU_BETTER(f2, t2, i2) ((f2) && (!cf || (t2) < ct || ((t2) == ct && (i2) < ci)))
+        { const int f2 = nu_quad_i<NU_QP_XOR1>(cf); const float t2 = nu_quad_f<NU_QP_XOR1>(ct); const int i2 = nu_quad_i<NU_QP_XOR1>(ci);
+          if (NU_BETTER(f2, t2, i2)) { cf = 1; ct = t2; ci = i2; } }
+        { const int f2 = nu_quad_i<NU_QP_XOR2>(cf); const float t2 = nu_quad_f<NU_QP_XOR2>(ct); const int i2 = nu_quad_i<NU_QP_XOR2>(ci);
+          if (NU_BETTER(f2, t2, i2)) { cf = 1; ct = t2; ci = i2; } }
+#undef NU_BETTER
+        if (cf && (!found || ct < best_t || (ct == best_t && ci < best_id))) { best_t = ct; best_id = ci; found = 1; }
+    };
+    if (n == 1) {
+        int cf = 0, ci = NU_MISS_INDEX;
+        float ct = 0.f, t;
+        if (sub == 0 && nu_ray_tri(o, d, tris, tris + 4, tris + 8, tmin, tmax, t)) { cf = 1; ct = t; ci = ids[0]; }
+        merge(cf, ct, ci);
+        return;
+    }
+    int sp = 0;
+    NuBvhWideEntry e = wide[sub];
+    while (true) {
+        float tn;
+        const bool hb = e.ref != NU_WIDE_EMPTY && nu_ray_box(o, invd, e.bmin, e.bmax, tmin, any_hit ? tmax : best_t, tn);
+        const bool leaf = hb && e.ref < 0;
+        const int pos = leaf ? -1 - e.ref : 0;
+        float tv[9];
+        int tid = NU_MISS_INDEX;
+        if (leaf) {
+#pragma unroll
+            for (int v = 0; v < 3; ++v)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) tv[v * 3 + k] = tris[pos * 12LL + v * 4 + k];
+            tid = ids[pos];
+        }
+        const int want = (hb && e.ref >= 0) ? 1 : 0;
+        int rank = 0, cnt = want;
+        { const int w2 = nu_quad_i<NU_QP_XOR1>(want); const float t2 = nu_quad_f<NU_QP_XOR1>(tn); const int s2 = sub ^ 1;
+          cnt += w2; rank += (w2 && (t2 < tn || (t2 == tn && s2 < sub))) ? 1 : 0; }
+        { const int w2 = nu_quad_i<NU_QP_XOR2>(want); const float t2 = nu_quad_f<NU_QP_XOR2>(tn); const int s2 = sub ^ 2;
+          cnt += w2; rank += (w2 && (t2 < tn || (t2 == tn && s2 < sub))) ? 1 : 0; }
+        { const int w2 = nu_quad_i<NU_QP_XOR3>(want); const float t2 = nu_quad_f<NU_QP_XOR3>(tn); const int s2 = sub ^ 3;
+          cnt += w2; rank += (w2 && (t2 < tn || (t2 == tn && s2 < sub))) ? 1 : 0; }
+        int next = (want && rank == 0) ? e.ref : -1;
+        next = max(next, nu_quad_i<NU_QP_XOR1>(next));
+        next = max(next, nu_quad_i<NU_QP_XOR2>(next));
+        if (want && rank > 0) stack[sp + (cnt - 1 - rank)][q] = e.ref;
+        sp += cnt > 0 ? cnt - 1 : 0;
+        bool done = false;
+        if (cnt == 0) {
+            if (sp == 0) done = true;
+            else next = stack[--sp][q];
+        }
+        NuBvhWideEntry e2 = e;
+        if (!done) e2 = wide[next * 4LL + sub];
+        int cf = 0, ci = NU_MISS_INDEX;
+        float ct = 0.f;
+        if (leaf) {
+            float t;
+            if (nu_ray_tri(o, d, tv, tv + 3, tv + 6, tmin, tmax, t)) { cf = 1; ct = t; ci = tid; }
+        }
+        merge(cf, ct, ci);
+        if (done || (any_hit && found)) break;
+        e = e2;
+    }
+}
+
+// The two meshes of a nested scene: as the entries take them, and as the kernels see them.
+#define NU_NESTED_ARGS const void* bvh_o, int n_faces_o, const float* V_o, const int* F_o, const float* vnormals_o, const float* ior, \
+                       const void* bvh_i, int n_faces_i, const float* V_i, const int* F_i, const float* vnormals_i, const float* materials_i
+struct NuNestedMeshes {
+    const char* __restrict__ bvh_o;        // outer shell: tree, vertices, faces, unit vertex normals, index of refraction per vertex
+    NuBvhLayout Lo;
+    const float* __restrict__ Vo;
+    const int* __restrict__ Fo;
+    const float* __restrict__ VNo;
+    const float* __restrict__ ior;
+    const char* __restrict__ bvh_i;        // inner object: tree, vertices, faces, unit vertex normals, materials [V,5]
+    NuBvhLayout Li;
+    const float* __restrict__ Vi;
+    const int* __restrict__ Fi;
+    const float* __restrict__ VNi;
+    const float* __restrict__ mat;
+};
+
+// Interior chain of the listed hit pixels of the OUTER G-buffer (whose rows carry the interpolated index of refraction - 1 in [10]):
+// one quad per pixel, 16 consecutive listed pixels per wave, every walk of a pixel's path in this one launch, state in registers.
+// Steps of a path: the reflection ray (any hit, outer), then per segment the closest hit against the inner and against the outer
+// tree, then the exit ray (any hit, outer).  DUMP writes every traced ray and what it met (tests).
+#define NU_RLN_PH_REFL 0
+#define NU_RLN_PH_INNER 1
+#define NU_RLN_PH_OUTER 2
+#define NU_RLN_PH_EXIT 3
+#define NU_RLN_PH_DONE 4
+template <bool DUMP>
+__global__ __launch_bounds__(64) void relight_nested_chain_kernel(NuNestedMeshes m, const float* __restrict__ gbuf, const int* __restrict__ pix,
+                                                                  int n_pix, float eps, int K, int* __restrict__ kind,
+                                                                  float* __restrict__ chain, float* __restrict__ irow,
+                                                                  float* __restrict__ seg, float* __restrict__ aux) {
+    __shared__ int stack[NU_WSTACK][16];
+    const int lane = threadIdx.x & 63, sub = lane & 3, q = lane >> 2;
+    const int i = blockIdx.x * 16 + q;
+    if (i >= n_pix) return;                                 // whole quads leave together
+    const float* g = gbuf + (long long)pix[i] * NU_RL_ROW;
+    float d0[3], x0[3], ng0[3], n[3], cur_o[3], cur_d[3], rdir[3];
+    for (int k = 0; k < 3; ++k) { d0[k] = -g[15 + k]; x0[k] = g[1 + k]; ng0[k] = g[4 + k]; }
+    float f_entry;
+    const bool enters = nu_rln_interface(d0, g + 7, 1.0f + g[10], true, n, cur_d, f_entry);
+    if (enters) nu_rln_reflect(d0, n, rdir);
+    else { for (int k = 0; k < 3; ++k) rdir[k] = cur_d[k]; }
+    const bool refl_traced = f_entry > 0.0f && nu_rl_dot3(n, rdir) > 0.0f && nu_rl_dot3(ng0, rdir) > 0.0f;
+    for (int k = 0; k < 3; ++k) cur_o[k] = x0[k] - eps * ng0[k];
+    float T = enters ? 1.0f - f_entry : 0.0f;
+    float refl_vis = 0.0f, exit_vis = 0.0f;
+    float exit_o[3] = {0.f, 0.f, 0.f}, exit_d[3] = {0.f, 0.f, 0.f};
+    int what = NU_RLN_DARK, k_seg = 0, n_walked = 0;
+    int in_found = 0, in_id = NU_MISS_INDEX;
+    float in_t = 0.0f;
+    int phase = refl_traced ? NU_RLN_PH_REFL : (enters ? NU_RLN_PH_INNER : NU_RLN_PH_DONE);
+    if (DUMP && sub == 0) {
+        float* a = aux + (long long)i * 16;
+        for (int k = 0; k < 3; ++k) { a[k] = x0[k] + eps * ng0[k]; a[3 + k] = rdir[k]; }
+        a[6] = refl_traced ? 1.0f : 0.0f; a[7] = 0.0f;
+        for (int k = 8; k < 16; ++k) a[k] = 0.0f;
+        for (int k = 0; k < K * 16; ++k) seg[(long long)i * K * 16 + k] = 0.0f;
+    }
+    while (phase != NU_RLN_PH_DONE) {
+        float o[3], d[3];
+        const bool outer = phase != NU_RLN_PH_INNER;
+        const bool any_hit = phase == NU_RLN_PH_REFL || phase == NU_RLN_PH_EXIT;
+        for (int k = 0; k < 3; ++k) {
+            o[k] = phase == NU_RLN_PH_REFL ? x0[k] + eps * ng0[k] : (phase == NU_RLN_PH_EXIT ? exit_o[k] : cur_o[k]);
+            d[k] = phase == NU_RLN_PH_REFL ? rdir[k] : (phase == NU_RLN_PH_EXIT ? exit_d[k] : cur_d[k]);
+        }
+        int found, id;
+        float t;
+        nu_walk_quad(stack, q, sub, outer ? m.bvh_o : m.bvh_i, outer ? m.Lo : m.Li, o, d, 0.0f, 1e16f, any_hit, found, id, t);
+        if (phase == NU_RLN_PH_REFL) {
+            refl_vis = found ? 0.0f : 1.0f;
+            if (DUMP && sub == 0) aux[(long long)i * 16 + 7] = found ? 1.0f : 0.0f;
+            phase = enters ? NU_RLN_PH_INNER : NU_RLN_PH_DONE;
+        } else if (phase == NU_RLN_PH_INNER) {
+            in_found = found; in_id = id; in_t = t;
+            phase = NU_RLN_PH_OUTER;
+        } else if (phase == NU_RLN_PH_OUTER) {
+            const bool ends_inner = in_found && (!found || in_t <= t);
+            ++n_walked;
+            float* sg = DUMP ? seg + ((long long)i * K + k_seg) * 16 : nullptr;
+            if (DUMP && sub == 0) {
+                for (int k = 0; k < 3; ++k) { sg[k] = cur_o[k]; sg[3 + k] = cur_d[k]; }
+                sg[6] = __int_as_float(ends_inner ? 1 : (found ? 2 : 0));
+                sg[7] = __int_as_float(ends_inner ? in_id : id);
+                sg[8] = ends_inner ? in_t : (found ? t : 0.0f);
+                sg[9] = __int_as_float(in_found); sg[10] = __int_as_float(in_id); sg[11] = in_found ? in_t : 0.0f;
+                sg[12] = __int_as_float(found); sg[13] = __int_as_float(id); sg[14] = found ? t : 0.0f;
+                sg[15] = __int_as_float(1);                                     // the segment was walked
+            }
+            if (ends_inner) {
+                float x[3], ng[3], ns[3], bary[3];
+                int vi[3];
+                nu_rl_surface(m.Vi, m.Fi, m.VNi, cur_o, cur_d, in_id, in_t, x, ng, ns, vi, bary);
+                if (sub == 0) {
+                    float* r = irow + (long long)i * NU_RL_ROW;
+                    r[0] = in_t;
+                    for (int k = 0; k < 3; ++k) { r[1 + k] = x[k]; r[4 + k] = ng[k]; r[7 + k] = ns[k]; r[15 + k] = -cur_d[k]; }
+                    for (int k = 0; k < 5; ++k)
+                        r[10 + k] = (bary[0] * m.mat[vi[0] * 5LL + k] + bary[1] * m.mat[vi[1] * 5LL + k]) + bary[2] * m.mat[vi[2] * 5LL + k];
+                    r[18] = g[18]; r[19] = g[19];
+                }
+                what = NU_RLN_INNER;
+                phase = NU_RLN_PH_DONE;
+            } else if (found) {
+                float keep, o2[3], d2[3];
+                const bool refr = nu_rln_leave(m.Vo, m.Fo, m.VNo, m.ior, cur_o, cur_d, id, t, eps, o2, d2, keep);
+                if (refr) {
+                    T = T * keep;
+                    for (int k = 0; k < 3; ++k) { exit_o[k] = o2[k]; exit_d[k] = d2[k]; }
+                    phase = NU_RLN_PH_EXIT;
+                } else {
+                    for (int k = 0; k < 3; ++k) { cur_o[k] = o2[k]; cur_d[k] = d2[k]; }     // total internal reflection: on, from eps inside
+                    ++k_seg;
+                    phase = k_seg < K ? NU_RLN_PH_INNER : NU_RLN_PH_DONE;
+                    if (k_seg >= K) T = 0.0f;
+                }
+            } else {                                        // a leaky shell: the ray leaves as it is, and nothing can shadow it
+                for (int k = 0; k < 3; ++k) { exit_o[k] = cur_o[k]; exit_d[k] = cur_d[k]; }
+                exit_vis = 1.0f;
+                what = NU_RLN_EXIT;
+                phase = NU_RLN_PH_DONE;
+            }
+        } else {
+            exit_vis = found ? 0.0f : 1.0f;
+            if (DUMP && sub == 0) {
+                float* a = aux + (long long)i * 16 + 8;
+                for (int k = 0; k < 3; ++k) { a[k] = exit_o[k]; a[3 + k] = exit_d[k]; }
+                a[6] = 1.0f; a[7] = found ? 1.0f : 0.0f;
+            }
+            what = NU_RLN_EXIT;
+            phase = NU_RLN_PH_DONE;
+        }
+    }
+    if (sub == 0) {
+        kind[i] = what;
+        float* c = chain + (long long)i * NU_RLN_CHAIN;
+        c[0] = what == NU_RLN_DARK ? 0.0f : T;
+        for (int k = 0; k < 3; ++k) { c[1 + k] = exit_d[k]; c[5 + k] = rdir[k]; }
+        c[4] = exit_vis; c[8] = f_entry; c[9] = refl_vis;
+        c[10] = __int_as_float(n_walked); c[11] = 0.0f;
+        if (what != NU_RLN_INNER) { for (int k = 0; k < NU_RL_ROW; ++k) irow[(long long)i * NU_RL_ROW + k] = 0.0f; }
+    }
+}
+
+// Light paths of the listed inner rows: blocks of 16 quads = 16 consecutive samples of one pixel (as NuRelightShadow), the three walks
+// of a sample back to back on the one stack, no ray stored: (a) any hit against the inner tree, (b) closest hit against the outer
+// tree along the same ray, the interface event going out, (c) any hit against the outer tree along the exit ray.  Per sample one
+// 16-byte record: (exit direction, 1 - F_exit), or zero for a dark sample; nu_relight_nested_resolve taps the environment.
+template <bool DUMP>
+__global__ __launch_bounds__(64) void relight_nested_light_kernel(NuNestedMeshes m, const float* __restrict__ irow, const int* __restrict__ sel,
+                                                                  int S, int s0, int s_count, int bpp, unsigned seed, float eps,
+                                                                  float4* __restrict__ rec, float* __restrict__ dump) {
+    __shared__ int stack[NU_WSTACK][16];
+    const int lane = threadIdx.x & 63, sub = lane & 3, q = lane >> 2;
+    const int i = blockIdx.x / bpp;
+    const int c = (blockIdx.x - i * bpp) * 16 + q;
+    if (c >= s_count) return;                               // whole quads leave together
+    const long long slot = (long long)i * s_count + c;
+    float o[3], d[3];
+    unsigned bits[2];
+    const bool traced = nu_relight_shadow_ray(irow + (long long)sel[i] * NU_RL_ROW, S, s0 + c, seed, eps, o, d, bits);
+    float4 out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float keep = 1.0f;
+    float* dp = DUMP ? dump + slot * NU_RLN_LIGHT_DUMP : nullptr;
+    if (DUMP && sub == 0) {
+        for (int k = 0; k < NU_RLN_LIGHT_DUMP; ++k) dp[k] = 0.0f;
+        for (int k = 0; k < 3; ++k) { dp[k] = o[k]; dp[3 + k] = d[k]; }
+        dp[6] = traced ? 1.0f : 0.0f;
+    }
+    int phase = traced ? 0 : 3;
+    while (phase != 3) {
+        int found, id;
+        float t;
+        nu_walk_quad(stack, q, sub, phase == 0 ? m.bvh_i : m.bvh_o, phase == 0 ? m.Li : m.Lo, o, d, 0.0f, 1e16f, phase != 1, found, id, t);
+        if (phase == 0) {
+            if (DUMP && sub == 0) dp[7] = found ? 1.0f : 0.0f;
+            phase = found ? 3 : 1;
+        } else if (phase == 1) {
+            if (DUMP && sub == 0) { dp[8] = found ? 1.0f : 0.0f; dp[9] = __int_as_float(id); dp[10] = found ? t : 0.0f; }
+            if (!found) {                                   // a leaky shell: the direction leaves unrefracted
+                out = make_float4(d[0], d[1], d[2], 1.0f);
+                phase = 3;
+            } else {
+                float o2[3], d2[3];
+                const bool refr = nu_rln_leave(m.Vo, m.Fo, m.VNo, m.ior, o, d, id, t, eps, o2, d2, keep);
+                if (DUMP && sub == 0) {
+                    dp[11] = refr ? 1.0f : 0.0f;
+                    for (int k = 0; k < 3; ++k) { dp[12 + k] = o2[k]; dp[15 + k] = d2[k]; }
+                    dp[19] = keep;
+                }
+                for (int k = 0; k < 3; ++k) { o[k] = o2[k]; d[k] = d2[k]; }
+                phase = refr ? 2 : 3;
+            }
+        } else {
+            if (DUMP && sub == 0) dp[18] = found ? 1.0f : 0.0f;
+            if (!found) out = make_float4(d[0], d[1], d[2], keep);
+            phase = 3;
+        }
+    }
+    if (sub == 0) rec[slot] = out;
+}
+
+static int nu_nested_meshes(NU_NESTED_ARGS, NuNestedMeshes& m) {
+    if (n_faces_o <= 0 || n_faces_i <= 0) return NU_ERR_ARG;
+    if (!bvh_o || !V_o || !F_o || !vnormals_o || !ior || !bvh_i || !V_i || !F_i || !vnormals_i || !materials_i) return NU_ERR_ARG;
+    m.bvh_o = (const char*)bvh_o; m.Lo = nu_bvh_layout(n_faces_o); m.Vo = V_o; m.Fo = F_o; m.VNo = vnormals_o; m.ior = ior;
+    m.bvh_i = (const char*)bvh_i; m.Li = nu_bvh_layout(n_faces_i); m.Vi = V_i; m.Fi = F_i; m.VNi = vnormals_i; m.mat = materials_i;
+    return NU_OK;
+}
+#define NU_NESTED_PASS bvh_o, n_faces_o, V_o, F_o, vnormals_o, ior, bvh_i, n_faces_i, V_i, F_i, vnormals_i, materials_i
+
+static int nu_nested_chain_launch(NU_NESTED_ARGS, const float* gbuf, const int* pix, int n_pix, float eps, int max_segments, int* kind,
+                                  float* chain, float* inner_rows, float* seg, float* aux, bool dump, hipStream_t stream) {
+    NuNestedMeshes m;
+    if (n_pix < 0 || max_segments < 1 || max_segments > 64 || nu_nested_meshes(NU_NESTED_PASS, m) != NU_OK) return NU_ERR_ARG;
+    if (n_pix == 0) return NU_OK;
+    if (!gbuf || !pix || !kind || !chain || !inner_rows || (dump && (!seg || !aux))) return NU_ERR_ARG;
+    const dim3 grid(nu_cdiv(n_pix, 16));
+    if (dump)
+        hipLaunchKernelGGL((relight_nested_chain_kernel<true>), grid, dim3(64), 0, stream, m, gbuf, pix, n_pix, eps, max_segments, kind,
+                           chain, inner_rows, seg, aux);
+    else
+        hipLaunchKernelGGL((relight_nested_chain_kernel<false>), grid, dim3(64), 0, stream, m, gbuf, pix, n_pix, eps, max_segments, kind,
+                           chain, inner_rows, seg, aux);
+    return nu_launch_status();
+}
+extern "C" int nu_relight_nested_chain(NU_NESTED_ARGS, const float* gbuf, const int* pix, int n_pix, float eps, int max_segments, int* kind,
+                                       float* chain, float* inner_rows, hipStream_t stream) {
+    return nu_nested_chain_launch(NU_NESTED_PASS, gbuf, pix, n_pix, eps, max_segments, kind, chain, inner_rows, nullptr, nullptr, false, stream);
+}
+extern "C" int nu_relight_nested_chain_dump(NU_NESTED_ARGS, const float* gbuf, const int* pix, int n_pix, float eps, int max_segments,
+                                            int* kind, float* chain, float* inner_rows, float* seg, float* aux, hipStream_t stream) {
+    return nu_nested_chain_launch(NU_NESTED_PASS, gbuf, pix, n_pix, eps, max_segments, kind, chain, inner_rows, seg, aux, true, stream);
+}
+
+static int nu_nested_light_launch(NU_NESTED_ARGS, const float* inner_rows, const int* sel, int n_sel, int samples, int s0, int s_count,
+                                  int seed, float eps, float* rec, float* dump, bool dumping, hipStream_t stream) {
+    NuNestedMeshes m;
+    if (n_sel < 0 || samples < 2 || (samples & 1) || s0 < 0 || s_count < 0 || s0 + s_count > samples) return NU_ERR_ARG;
+    if (nu_nested_meshes(NU_NESTED_PASS, m) != NU_OK) return NU_ERR_ARG;
+    if (n_sel == 0 || s_count == 0) return NU_OK;
+    if (!inner_rows || !sel || !rec || (dumping && !dump)) return NU_ERR_ARG;
+    const int bpp = nu_cdiv(s_count, 16);
+    const long long blocks = (long long)n_sel * bpp;
+    if (blocks > 0x7fffffffLL) return NU_ERR_ARG;         // the caller chunks over pixels / samples
+    if (dumping)
+        hipLaunchKernelGGL((relight_nested_light_kernel<true>), dim3((unsigned)blocks), dim3(64), 0, stream, m, inner_rows, sel, samples, s0,
+                           s_count, bpp, (unsigned)seed, eps, (float4*)rec, dump);
+    else
+        hipLaunchKernelGGL((relight_nested_light_kernel<false>), dim3((unsigned)blocks), dim3(64), 0, stream, m, inner_rows, sel, samples, s0,
+                           s_count, bpp, (unsigned)seed, eps, (float4*)rec, dump);
+    return nu_launch_status();
+}
+extern "C" int nu_relight_nested_light(NU_NESTED_ARGS, const float* inner_rows, const int* sel, int n_sel, int samples, int s0, int s_count,
+                                       int seed, float eps, float* rec, hipStream_t stream) {
+    return nu_nested_light_launch(NU_NESTED_PASS, inner_rows, sel, n_sel, samples, s0, s_count, seed, eps, rec, nullptr, false, stream);
+}
+extern "C" int nu_relight_nested_light_dump(NU_NESTED_ARGS, const float* inner_rows, const int* sel, int n_sel, int samples, int s0,
+                                            int s_count, int seed, float eps, float* rec, float* dump, hipStream_t stream) {
+    return nu_nested_light_launch(NU_NESTED_PASS, inner_rows, sel, n_sel, samples, s0, s_count, seed, eps, rec, dump, true, stream);
 }
 
 // brute-force closest hit on the device (same triangle test; O(N*F)): cross-check + tiny meshes

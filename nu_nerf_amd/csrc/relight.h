@@ -101,6 +101,105 @@ static __device__ inline bool nu_relight_shadow_ray(const float* g, int S, int s
     return traced;
 }
 
+// ---- the nested object: a transparent outer shell with a per-vertex index of refraction around an opaque inner mesh ----
+static __device__ inline float nu_rl_dot3(const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+static __device__ inline void nu_rl_cross(const float* a, const float* b, float* c) {
+    c[0] = a[1] * b[2] - a[2] * b[1];
+    c[1] = a[2] * b[0] - a[0] * b[2];
+    c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// What nu_relight_gbuffer derives at a hit, for the hit of ray (o, d) with face `id` at distance t: the point x, the unit geometric
+// normal ng facing the viewer (against d), the unit interpolated normal ns on ng's side (same degenerate fallbacks), the vertex ids
+// and the barycentric weights bary = (w0, u, v) -- the operations of the ray / triangle test in its order.
+static __device__ inline void nu_rl_surface(const float* __restrict__ V, const int* __restrict__ F, const float* __restrict__ VN,
+                                            const float* o, const float* d, int id, float t, float* x, float* ng, float* ns, int* vi,
+                                            float* bary) {
+    vi[0] = F[id * 3LL]; vi[1] = F[id * 3LL + 1]; vi[2] = F[id * 3LL + 2];
+    float v0[3], e1[3], e2[3], pv[3], tv[3], qv[3], view[3];
+    for (int k = 0; k < 3; ++k) {
+        v0[k] = V[vi[0] * 3LL + k];
+        e1[k] = V[vi[1] * 3LL + k] - v0[k];
+        e2[k] = V[vi[2] * 3LL + k] - v0[k];
+        view[k] = -d[k];
+    }
+    nu_rl_cross(d, e2, pv);
+    const float inv = 1.0f / nu_rl_dot3(e1, pv);
+    for (int k = 0; k < 3; ++k) tv[k] = o[k] - v0[k];
+    const float u = nu_rl_dot3(tv, pv) * inv;
+    nu_rl_cross(tv, e1, qv);
+    const float v = nu_rl_dot3(d, qv) * inv;
+    const float w0 = (1.0f - u) - v;
+    nu_rl_cross(e1, e2, ng);
+    float len = sqrtf(nu_rl_dot3(ng, ng));
+    if (len > 0.0f) { for (int k = 0; k < 3; ++k) ng[k] = ng[k] / len; }
+    else { for (int k = 0; k < 3; ++k) ng[k] = view[k]; }
+    if (nu_rl_dot3(ng, view) < 0.0f) { for (int k = 0; k < 3; ++k) ng[k] = -ng[k]; }
+    for (int k = 0; k < 3; ++k) ns[k] = (w0 * VN[vi[0] * 3LL + k] + u * VN[vi[1] * 3LL + k]) + v * VN[vi[2] * 3LL + k];
+    len = sqrtf(nu_rl_dot3(ns, ns));
+    if (len > 0.0f && len < 1e30f) { for (int k = 0; k < 3; ++k) ns[k] = ns[k] / len; }
+    else { for (int k = 0; k < 3; ++k) ns[k] = ng[k]; }
+    if (nu_rl_dot3(ns, ng) < 0.0f) { for (int k = 0; k < 3; ++k) ns[k] = -ns[k]; }
+    for (int k = 0; k < 3; ++k) x[k] = o[k] + t * d[k];
+    bary[0] = w0; bary[1] = u; bary[2] = v;
+}
+
+// The interface event of direction d (unit) at a point of the outer mesh with unit shading normal ns and index of refraction ior >= 1,
+// entering from air (eta = 1 / ior) or leaving (eta = ior).  n = ns oriented against d; cos_i = -n.d; total internal reflection exactly
+// as the stage-2 model was trained (s2_refract_fwd_kernel): no refraction when eta^2 sin^2_i > 0.999.  Returns true when the ray
+// refracts: dn = eta d + (eta cos_i - sqrt(1 - eta^2 sin^2_i)) n, renormalised; fres = Schlick, F0 + (1 - F0)(1 - c)^5 with
+// F0 = ((ior - 1) / (ior + 1))^2 and c the cosine on the AIR side (cos_i entering, the refracted cosine leaving), which makes a
+// crossing reciprocal.  F0 = 0 (ior = 1, an index-matched interface) reflects nothing: fres = 0.  Returns false on total internal
+// reflection: dn = d + 2 cos_i n, fres = 1 (0 when F0 = 0).
+static __device__ inline bool nu_rln_interface(const float* d, const float* ns, float ior, bool entering, float* n, float* dn,
+                                               float& fres) {
+    const float sg = nu_rl_dot3(ns, d) > 0.0f ? -1.0f : 1.0f;
+    for (int k = 0; k < 3; ++k) n[k] = sg * ns[k];
+    const float cos_i = -nu_rl_dot3(n, d);
+    const float sin2_i = 1.0f - cos_i * cos_i;
+    const float eta = entering ? 1.0f / ior : ior;
+    const float k2 = eta * eta * sin2_i;
+    const float r = (ior - 1.0f) / (ior + 1.0f), f0 = r * r;
+    if (k2 > 0.999f) {
+        for (int k = 0; k < 3; ++k) dn[k] = d[k] + (2.0f * cos_i) * n[k];
+        fres = f0 > 0.0f ? 1.0f : 0.0f;
+        return false;
+    }
+    const float cos_t = sqrtf(1.0f - k2);
+    const float f = eta * cos_i - cos_t;
+    float tv[3];
+    for (int k = 0; k < 3; ++k) tv[k] = eta * d[k] + f * n[k];
+    const float len = sqrtf(nu_rl_dot3(tv, tv));
+    for (int k = 0; k < 3; ++k) dn[k] = tv[k] / len;
+    const float m = fmaxf(1.0f - (entering ? cos_i : cos_t), 0.0f);
+    fres = f0 > 0.0f ? f0 + (1.0f - f0) * ((m * m) * (m * m) * m) : 0.0f;
+    return true;
+}
+
+// The mirror direction of the entry event: reflect(d, n) = d - 2 (n.d) n for the oriented normal n.
+static __device__ inline void nu_rln_reflect(const float* d, const float* n, float* r) {
+    const float c = -nu_rl_dot3(n, d);
+    for (int k = 0; k < 3; ++k) r[k] = d[k] + (2.0f * c) * n[k];
+}
+
+// Light path of a sample, second half: the ray (o, d) from the inner object met face `id` of the outer mesh at distance t from inside.
+// Returns true when it refracts: (o2, d2) is the exit ray -- the hit point pushed eps along the OUTWARD geometric normal, the refracted
+// direction -- and keep = 1 - F_exit.  Returns false on total internal reflection: (o2, d2) is the mirrored ray restarted eps on the
+// INSIDE of the hit point (the interior chain goes on with it; a light path takes no interior bounce and is dark).
+static __device__ inline bool nu_rln_leave(const float* __restrict__ V, const int* __restrict__ F, const float* __restrict__ VN,
+                                                const float* __restrict__ ior, const float* o, const float* d, int id, float t,
+                                                float eps, float* o2, float* d2, float& keep) {
+    float x[3], ng[3], ns[3], n[3], bary[3], fres;
+    int vi[3];
+    nu_rl_surface(V, F, VN, o, d, id, t, x, ng, ns, vi, bary);
+    // the excess over 1 is what is interpolated (as the G-buffer pass does for the primary hit): a constant index stays that index, bit for bit
+    const float index = 1.0f + ((bary[0] * (ior[vi[0]] - 1.0f) + bary[1] * (ior[vi[1]] - 1.0f)) + bary[2] * (ior[vi[2]] - 1.0f));
+    const bool refr = nu_rln_interface(d, ns, index, false, n, d2, fres);
+    for (int k = 0; k < 3; ++k) o2[k] = refr ? x[k] - eps * ng[k] : x[k] + eps * ng[k];
+    keep = 1.0f - fres;
+    return refr;
+}
+
 // Lat-long environment, z up: column u = (1/2 - atan2(d.y, d.x) / 2 pi) * W, row v = atan2(hypot(d.x, d.y), d.z) / pi * H (row 0 = +z);
 // texel centres at half-integers, bilinear, wrapping in u and clamping in v.  env = RGBA fp32 [H, W]: a tap is one 16-byte load.
 static __device__ inline void nu_relight_env(const float4* __restrict__ env, int eh, int ew, const float* d, float* rgb) {

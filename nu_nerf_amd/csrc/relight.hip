@@ -52,6 +52,72 @@ extern "C" int nu_relight_resolve(const float* gbuf, const int* pix, int n_pix, 
     return nu_launch_status();
 }
 
+// Resolve of the nested object: one thread per listed pixel (sel = indices into kind / chain / inner_rows, opix = the
+// G-buffer row each of them writes).  An inner pixel adds T * weight * (1 - F_exit) * env(d_out) * scale of the samples [s0, s0 + s_count)
+// in sample order (rec: their records, weights regenerated from the inner row); with last != 0 -- the call that ends a pixel -- the
+// reflection term F_entry * env(r) * vis and, for an exit pixel, T * env(d_exit) * vis are added after the samples.  No atomics.
+__global__ __launch_bounds__(256) void relight_nested_resolve_kernel(const float* __restrict__ irow, const float* __restrict__ chain,
+                                                                     const int* __restrict__ kind, const int* __restrict__ opix,
+                                                                     const int* __restrict__ sel, int n_sel, int S, int s0, int s_count,
+                                                                     unsigned seed, const float4* __restrict__ env, int eh, int ew,
+                                                                     const float4* __restrict__ rec, float scale, int last,
+                                                                     float* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_sel) return;
+    const long long j = sel[i], row = opix[j];
+    const float* ch = chain + j * NU_RLN_CHAIN;
+    const int what = kind[j];
+    const float T = ch[0];
+    float acc[3];
+    for (int c = 0; c < 3; ++c) acc[c] = out[row * 4 + c];
+    if (what == NU_RLN_INNER && s_count > 0) {
+        float g[NU_RL_ROW];
+#pragma unroll
+        for (int k = 0; k < NU_RL_ROW; k += 4) {
+            const float4 q = *(const float4*)(irow + j * NU_RL_ROW + k);
+            g[k] = q.x; g[k + 1] = q.y; g[k + 2] = q.z; g[k + 3] = q.w;
+        }
+        const float4* r = rec + (long long)i * s_count;
+        for (int c = 0; c < s_count; ++c) {
+            const float4 e = r[c];
+            if (e.w == 0.0f) continue;
+            int lobe;
+            float l[3], hv[3], rad[3], wgt[3];
+            unsigned bits[2];
+            nu_relight_sample(g, S, s0 + c, seed, lobe, l, hv, bits);
+            const float dout[3] = {e.x, e.y, e.z};
+            nu_relight_env(env, eh, ew, dout, rad);
+            nu_relight_weight(g, lobe, l, hv, wgt);
+            for (int k = 0; k < 3; ++k) acc[k] = acc[k] + (T * ((wgt[k] * e.w) * rad[k])) * scale;
+        }
+    }
+    if (last) {
+        float rad[3];
+        if (ch[8] > 0.0f && ch[9] > 0.0f) {
+            nu_relight_env(env, eh, ew, ch + 5, rad);
+            for (int k = 0; k < 3; ++k) acc[k] = acc[k] + ch[8] * rad[k];
+        }
+        if (what == NU_RLN_EXIT && ch[4] > 0.0f) {
+            nu_relight_env(env, eh, ew, ch + 1, rad);
+            for (int k = 0; k < 3; ++k) acc[k] = acc[k] + T * rad[k];
+        }
+    }
+    for (int c = 0; c < 3; ++c) out[row * 4 + c] = acc[c];
+    out[row * 4 + 3] = 1.0f;
+}
+
+extern "C" int nu_relight_nested_resolve(const float* inner_rows, const float* chain, const int* kind, const int* opix, const int* sel,
+                                         int n_sel, int samples, int s0, int s_count, int seed, const float* env, int env_h, int env_w,
+                                         const float* rec, float scale, int last, float* out, hipStream_t stream) {
+    if (n_sel < 0 || samples < 2 || (samples & 1) || s0 < 0 || s_count < 0 || s0 + s_count > samples || env_h <= 0 || env_w <= 0)
+        return NU_ERR_ARG;
+    if (n_sel == 0 || (s_count == 0 && !last)) return NU_OK;
+    if (!inner_rows || !chain || !kind || !opix || !sel || !env || !out || (s_count > 0 && !rec)) return NU_ERR_ARG;
+    hipLaunchKernelGGL(relight_nested_resolve_kernel, dim3(nu_cdiv(n_sel, 256)), dim3(256), 0, stream, inner_rows, chain, kind, opix, sel,
+                       n_sel, samples, s0, s_count, (unsigned)seed, (const float4*)env, env_h, env_w, (const float4*)rec, scale, last, out);
+    return nu_launch_status();
+}
+
 // exactly the rays nu_relight_visibility makes (the same device function), written out: rays [n_pix * s_count, 6]; bits (optional)
 // [n_pix * s_count, 3] = the two 24-bit sample integers and 1 where the ray is traced
 __global__ __launch_bounds__(256) void relight_shadow_rays_kernel(const float* __restrict__ gbuf, const int* __restrict__ pix, int n_pix,

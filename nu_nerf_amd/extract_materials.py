@@ -7,7 +7,10 @@ the directory relight.py --material takes (blender_backend/relight_backend.py:26
 
 --mesh defaults to data/meshes/{name}-{step}.ply, the file extract_mesh writes for the same checkpoint; --out to
 data/materials/{name}-{step}.  --stage2: a stage-2 config; --inner (default) bakes the inner networks, --outer the stage-1 networks
-the stage-2 model carries.  --ply also writes DIR/{mesh stem}_albedo.ply: the mesh with the albedo as uint8 vertex colours.
+the stage-2 model carries; both also write DIR/ior.npy [V_outer,1], the learned index of refraction at the vertices of the outer
+shell (materials.predict_ior) that relight --ior DIR takes.  With --inner the shell is the stage-1 mesh of the config
+(stage1_mesh_dir), NOT --mesh: ior.npy is in that file's vertex order, and that same file is what relight --mesh must be given
+(relight checks the vertex count only).  --ply also writes DIR/{mesh stem}_albedo.ply: the mesh with the albedo as uint8 vertex colours.
 """
 import argparse
 import os
@@ -46,6 +49,20 @@ def output_paths(flags, name, step):
     return mesh, out, (os.path.join(out, stem + '_albedo.ply') if flags.ply else None)
 
 
+def ior_mesh(flags, network, baked):
+    """The mesh whose vertices get an index of refraction: the outer shell.  --outer bakes that mesh, so it is `baked`; otherwise the
+    stage-1 mesh the stage-2 model refracts through."""
+    return baked if flags.outer else network._mesh
+
+
+def save_ior(out, ior):
+    """DIR/ior.npy [V,1] float32: what relight --ior DIR reads."""
+    import numpy as np
+    ior = np.ascontiguousarray(ior, np.float32).reshape(-1, 1)
+    np.save(os.path.join(out, 'ior.npy'), ior)
+    return os.path.join(out, 'ior.npy')
+
+
 def main(argv=None):
     flags = parse_args(argv)
     import numpy as np
@@ -53,7 +70,7 @@ def main(argv=None):
     import yaml
     from . import mesh as M
     from .extract_mesh import _renderer
-    from .materials import predict_materials
+    from .materials import predict_ior, predict_materials
     from .train_glue import load_checkpoint
 
     with open(flags.cfg) as fh:
@@ -78,6 +95,9 @@ def main(argv=None):
     for k in ('metallic', 'roughness', 'albedo'):
         np.save(os.path.join(out, k + '.npy'), mats[k].astype(np.float32))
     print(f'wrote {out}/metallic.npy, roughness.npy, albedo.npy: {len(V)} vertices of {mesh_path}')
+    if flags.stage2:
+        save_ior(out, predict_ior(network, ior_mesh(flags, network, (V, F))))
+        print(f'wrote {out}/ior.npy')
     if ply_path:
         M.write_ply(ply_path, V, F, colors=mats['albedo'])
         print(f'wrote {ply_path}')

@@ -109,3 +109,22 @@ def predict_materials(renderer, mesh=None, which=None):
     dev = next(renderer.parameters()).device
     out = bake_materials(renderer, torch.from_numpy(V).to(dev), which=which)
     return {k: out[k].cpu().numpy() for k in ('metallic', 'roughness', 'albedo')}
+
+
+@torch.no_grad()
+def predict_ior(renderer, mesh=None):
+    """Per-vertex index of refraction [V,1] float32 (numpy) of the OUTER mesh of a stage-2 model, in the vertex order of `mesh` (as
+    mesh_vertices reads it): the IoR network as the stage-2 light paths evaluate it (stage2.trace_segments: sigmoid of the network on
+    the 6-frequency embedding of the point), turned into the physical index exactly as the refraction kernel does
+    (s2_refract_fwd_kernel: eta = 1 / (ior * 1 + 1) entering from air), i.e. index = sigmoid(net(x)) + 1, in (1, 2).  This is what
+    relight --ior takes."""
+    if not _is_stage2(renderer):
+        raise ValueError("predict_ior: only a stage-2 renderer has an index-of-refraction network")
+    from . import torch_glue as G
+    V = mesh_vertices(renderer, mesh)
+    dev = next(renderer.parameters()).device
+    x = torch.from_numpy(V).to(dev)
+    if x.shape[0] == 0:
+        return np.zeros((0, 1), np.float32)
+    raw = torch.sigmoid(renderer.nets()[1].ior(G.embed(x, 6)))
+    return (raw.reshape(-1, 1) * 1.0 + 1.0).cpu().numpy().astype(np.float32)

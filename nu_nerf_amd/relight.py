@@ -1,5 +1,5 @@
 """python -m nu_nerf_amd.relight --mesh PLY --material DIR --hdr FILE --name NAME [--trans] [--num 360 --width 800 --height 800
---samples 1024 --cam_dist 3.0 --azimuth 0 --elevation 45]
+--samples 1024 --cam_dist 3.0 --azimuth 0 --elevation 45] [--inner PLY --inner-material DIR --ior VALUE_OR_DIR]
 
 relight.py + blender_backend/relight_backend.py on the GPU: the extracted mesh, the per-vertex DIR/metallic.npy, roughness.npy and
 albedo.npy that extract_materials writes and a lat-long HDR environment map are rendered from the reference's camera orbit
@@ -8,6 +8,11 @@ skipped (relight_backend.py:82).  Blender is not involved: primary visibility, a
 traced on the HIP LBVH (nu_relight_gbuffer, nu_relight_visibility) and shaded by nu_relight_resolve with the material model the
 networks were trained under.  DESIGN.md 20 defines the light transport and lists what is not Cycles; nothing here is pinned
 against Blender output.
+
+--inner: the nested object of stage 2.  --mesh is then the transparent outer shell, --inner the cleaned inner mesh with its baked
+--inner-material, --ior the shell's index of refraction: a number (default 1.5) or the directory whose ior.npy [V,1]
+extract_materials --stage2 wrote; --material is not needed.  The view refracts into the shell, the inner object is lit through it
+(DESIGN.md 21).  --trans turns both meshes.
 
 --hdr takes a Radiance .hdr (RGBE, flat or run-length scanlines) or a .npy float [H,W,3]; the map is z up in the mesh's frame.
 --focal_mm / --sensor_mm: Blender's default camera (50 mm on a 36 mm sensor fitted to the larger image side).  --seed, --chunk
@@ -298,6 +303,136 @@ def relight(V, F, materials, env, poses, h, w, samples, seed=0, chunk=256, **kw)
     return to_srgb8(relight_linear(V, F, materials, env, poses, h, w, samples, seed, chunk, **kw))
 
 
+# ---- the nested object ------------------------------------------------------------------------------------------------
+MAX_SEGMENTS = 4                # NU_RLN_MAX_SEGMENTS: interior segments of a camera path before the pixel counts as dark
+CHAIN = 12                      # floats per chain record (include/nu_nerf.h)
+DARK, INNER, EXIT = 0, 1, 2     # terminal kinds of a pixel's interior chain
+SEG, LIGHT_DUMP = 16, 20        # floats per dumped segment / light path
+
+
+class NestedScene:
+    """A transparent outer shell around an opaque inner mesh: two Scenes (each mesh + LBVH + vertex normals) and the per-vertex index
+    of refraction of the shell.  ior: a scalar or [V_o] / [V_o,1], every value finite and >= 1.  The outer Scene's material table holds
+    the index minus 1 in column 0, so that the G-buffer pass interpolates it with the barycentrics of the primary hit."""
+
+    def __init__(self, V_o, F_o, ior, V_i, F_i, materials_i, device=None):
+        import torch
+        nv = int(V_o.shape[0])
+        ior = np.asarray(ior.cpu() if torch.is_tensor(ior) else ior, np.float32)
+        ior = np.full(nv, float(ior), np.float32) if ior.ndim == 0 else ior.reshape(-1)
+        if ior.shape != (nv,):
+            raise ValueError(f"ior must be a scalar or give one value for each of the {nv} outer vertices, got {ior.shape}")
+        if not np.isfinite(ior).all() or (ior < 1.0).any():
+            raise ValueError("ior must be finite and >= 1")
+        mo = np.zeros((nv, 5), np.float32)
+        mo[:, 0] = ior - 1.0
+        self.outer = Scene(V_o, F_o, mo, device)
+        self.inner = Scene(V_i, F_i, materials_i, self.outer.device)
+        self.ior = torch.from_numpy(ior).to(self.outer.device)
+        self.device = self.outer.device
+
+    def _args(self):
+        from . import _lib as L
+        o, i = self.outer, self.inner
+        return (L.ptr(o.bvh.buf), o.bvh.n_faces, L.ptr(o.V), L.ptr(o.F), L.ptr(o.normals), L.ptr(self.ior),
+                L.ptr(i.bvh.buf), i.bvh.n_faces, L.ptr(i.V), L.ptr(i.F), L.ptr(i.normals), L.ptr(i.materials))
+
+
+def nested_chain(ns, gbuf, pix, eps=ORIGIN_EPS, max_segments=MAX_SEGMENTS, dump=False):
+    """The interior chain of the listed hit pixels of the OUTER G-buffer -> kind int32 [n], chain float32 [n, CHAIN], inner rows
+    float32 [n, ROW]; with dump also seg [n, max_segments, SEG] and aux [n, 2, 8] (see include/nu_nerf.h)."""
+    import torch
+    from . import _lib as L
+    n = int(pix.shape[0])
+    kind = torch.empty(n, dtype=torch.int32, device=ns.device)
+    chain = torch.empty(n, CHAIN, dtype=torch.float32, device=ns.device)
+    irow = torch.empty(n, ROW, dtype=torch.float32, device=ns.device)
+    if not dump:
+        L.load().nu_relight_nested_chain(*ns._args(), L.ptr(gbuf), L.ptr(pix), n, float(eps), int(max_segments), L.ptr(kind), L.ptr(chain),
+                                         L.ptr(irow), L.stream())
+        return kind, chain, irow
+    seg = torch.empty(n, int(max_segments), SEG, dtype=torch.float32, device=ns.device)
+    aux = torch.empty(n, 2, 8, dtype=torch.float32, device=ns.device)
+    L.load().nu_relight_nested_chain_dump(*ns._args(), L.ptr(gbuf), L.ptr(pix), n, float(eps), int(max_segments), L.ptr(kind), L.ptr(chain),
+                                          L.ptr(irow), L.ptr(seg), L.ptr(aux), L.stream())
+    return kind, chain, irow, seg, aux
+
+
+def nested_light(ns, irow, sel, samples, s0, s_count, seed, eps=ORIGIN_EPS, dump=False):
+    """rec float32 [n_sel, s_count, 4] = (exit direction, 1 - F_exit) of the light path of sample s0 + c of inner pixel sel[i], zero
+    where it is dark; with dump also [n_sel * s_count, LIGHT_DUMP]."""
+    import torch
+    from . import _lib as L
+    n = int(sel.shape[0])
+    rec = torch.empty(n, int(s_count), 4, dtype=torch.float32, device=ns.device)
+    if not dump:
+        L.load().nu_relight_nested_light(*ns._args(), L.ptr(irow), L.ptr(sel), n, int(samples), int(s0), int(s_count), _seed(seed), float(eps),
+                                         L.ptr(rec), L.stream())
+        return rec
+    d = torch.empty(n * int(s_count), LIGHT_DUMP, dtype=torch.float32, device=ns.device)
+    L.load().nu_relight_nested_light_dump(*ns._args(), L.ptr(irow), L.ptr(sel), n, int(samples), int(s0), int(s_count), _seed(seed),
+                                          float(eps), L.ptr(rec), L.ptr(d), L.stream())
+    return rec, d
+
+
+def nested_resolve(irow, chain, kind, opix, sel, samples, s0, s_count, seed, env, rec, last, out):
+    """out [rows of the outer G-buffer, 4] += the samples [s0, s0 + s_count) of the listed pixels; last: also their reflection and
+    exit terms (the call that ends these pixels)."""
+    from . import _lib as L
+    L.load().nu_relight_nested_resolve(L.ptr(irow), L.ptr(chain), L.ptr(kind), L.ptr(opix), L.ptr(sel), int(sel.shape[0]), int(samples),
+                                       int(s0), int(s_count), _seed(seed), L.ptr(env), int(env.shape[0]), int(env.shape[1]), L.ptr(rec),
+                                       2.0 / samples, 1 if last else 0, L.ptr(out), L.stream())
+    return out
+
+
+def relight_nested_linear(scene, env, poses, h, w, samples, seed=0, chunk=256, rows=None, images=1, K=None, img0=0, eps=ORIGIN_EPS,
+                          max_segments=MAX_SEGMENTS):
+    """relight_linear for a NestedScene: linear radiance float32 [n,h,w,4], alpha 1 where the primary ray hits the OUTER mesh.  The same
+    piece / sample chunking with the same guarantee: the result does not depend on `images`, `rows` or `chunk`, bit for bit.  Device
+    memory besides the meshes, the environment and the result: 232 bytes per pixel of a piece (outer row, face id, hit list, chain
+    record, kind, inner row) plus at most VIS_BYTES of 16-byte sample records."""
+    import torch
+    from .mask_render import _cams
+    samples, chunk = int(samples), int(chunk)
+    if samples < 2 or samples % 2:
+        raise ValueError(f"samples must be even and >= 2, got {samples}")
+    if chunk < 1 or images < 1 or (rows is not None and rows < 1):
+        raise ValueError("chunk, rows and images must be >= 1")
+    dev = scene.device
+    poses = np.asarray(poses.cpu() if torch.is_tensor(poses) else poses, np.float64).reshape(-1, 3, 4)
+    K = intrinsics(h, w) if K is None else np.asarray(K, np.float64)
+    cams = _cams(K.astype(np.float32), poses.astype(np.float32), dev)
+    envd = torch.from_numpy(pack_env(env)).to(dev)
+    n, rows = int(cams.shape[0]), int(rows or h)
+    out = torch.zeros(n, h, w, 4, dtype=torch.float32, device=dev)
+    sc_max = min(chunk, samples)
+    per = max(1, min(VIS_BYTES // (16 * sc_max), (2 ** 31 - 1) // ((sc_max + 15) // 16)))
+    for i0 in range(0, n, images):
+        ni = min(images, n - i0)
+        for y0 in range(0, h, rows):
+            nr = min(rows, h - y0)
+            face, gbuf = gbuffer(scene.outer, cams[i0:i0 + ni], h, w, img0 + i0, y0, nr)
+            pix = hit_pixels(face)
+            piece = torch.zeros(ni * nr * w, 4, dtype=torch.float32, device=dev)
+            kind, chain, irow = nested_chain(scene, gbuf, pix, eps, max_segments)
+            inner = (kind == INNER).nonzero().flatten().to(torch.int32)
+            other = (kind != INNER).nonzero().flatten().to(torch.int32)
+            nested_resolve(irow, chain, kind, pix, other, samples, 0, 0, seed, envd, None, True, piece)
+            for p0 in range(0, int(inner.shape[0]), per):
+                sel = inner[p0:p0 + per].contiguous()
+                for s0 in range(0, samples, chunk):
+                    sc = min(chunk, samples - s0)
+                    rec = nested_light(scene, irow, sel, samples, s0, sc, seed, eps)
+                    nested_resolve(irow, chain, kind, pix, sel, samples, s0, sc, seed, envd, rec, s0 + sc == samples, piece)
+            out[i0:i0 + ni, y0:y0 + nr] = piece.reshape(ni, nr, w, 4)
+    return out
+
+
+def relight_nested(scene, env, poses, h, w, samples, seed=0, chunk=256, **kw):
+    """uint8 [n,h,w,4] sRGB + alpha of relight_nested_linear (same arguments)."""
+    return to_srgb8(relight_nested_linear(scene, env, poses, h, w, samples, seed, chunk, **kw))
+
+
 def write_png(path, rgba):
     """RGBA uint8 [h,w,4] as a PNG (Pillow)."""
     from .mask_render import _pillow
@@ -312,10 +447,17 @@ def write_png(path, rgba):
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="python -m nu_nerf_amd.relight", description=__doc__.split("\n\n")[1])
     ap.add_argument('--mesh', type=str, required=True, help="triangle mesh (PLY)")
-    ap.add_argument('--material', type=str, required=True, help="directory with metallic.npy, roughness.npy, albedo.npy")
+    args = sys.argv[1:] if argv is None else list(argv)
+    # only with --inner may --material be left out.  The exact spelling is enough: every shorter prefix (--inn, --inne) is also one of
+    # --inner-material, which argparse refuses as ambiguous; abbreviations stay allowed, as the command without --inner always had them
+    nested = any(a == '--inner' or a.startswith('--inner=') for a in args)
+    ap.add_argument('--material', type=str, required=not nested, help="directory with metallic.npy, roughness.npy, albedo.npy")
     ap.add_argument('--hdr', type=str, required=True, help="environment map: Radiance .hdr or .npy float [H,W,3]")
     ap.add_argument('--name', type=str, required=True, help="frames go to data/relight/NAME")
     ap.add_argument('--trans', action='store_true', default=False, help="turn the mesh +90 degrees about x")
+    ap.add_argument('--inner', type=str, default=None, help="inner mesh (PLY): --mesh is then the transparent shell around it")
+    ap.add_argument('--inner-material', dest='inner_material', type=str, default=None, help="material directory of the inner mesh")
+    ap.add_argument('--ior', type=str, default='1.5', help="index of refraction of the shell: a number or a directory with ior.npy [V,1]")
     ap.add_argument('--output', type=str, default=None, help="output directory (default data/relight/NAME)")
     ap.add_argument('--width', type=int, default=800)
     ap.add_argument('--height', type=int, default=800)
@@ -333,7 +475,38 @@ def parse_args(argv=None):
         ap.error("--samples must be even and >= 2")
     if flags.num < 1 or flags.width < 1 or flags.height < 1 or flags.chunk < 1:
         ap.error("--num, --width, --height and --chunk must be >= 1")
+    if flags.inner is None:
+        if flags.inner_material is not None:
+            ap.error("--inner-material needs --inner")
+    else:
+        if flags.inner_material is None:
+            ap.error("--inner needs --inner-material")
+        try:
+            parse_ior(flags.ior)
+        except ValueError as e:
+            ap.error(str(e))
     return flags
+
+
+def parse_ior(text):
+    """--ior: a number >= 1 -> float, anything else -> the path DIR/ior.npy (a directory as extract_materials writes it)."""
+    try:
+        value = float(text)
+    except ValueError:
+        return os.path.join(text, 'ior.npy')
+    if not np.isfinite(value) or value < 1.0:
+        raise ValueError(f"--ior must be >= 1, got {text}")
+    return value
+
+
+def load_ior(spec, n_verts):
+    """float32 [n_verts] from what parse_ior returns: the scalar repeated, or the [V,1] array of the file."""
+    if isinstance(spec, float):
+        return np.full(n_verts, spec, np.float32)
+    a = np.load(spec)
+    if a.size != n_verts or a.shape not in ((n_verts,), (n_verts, 1)):
+        raise ValueError(f"{spec}: expected [{n_verts},1] (one index of refraction per vertex of the shell), got {a.shape}")
+    return np.ascontiguousarray(a, np.float32).reshape(-1)
 
 
 def output_dir(flags):
@@ -365,12 +538,21 @@ def main(argv=None):
     V, F = M.read_ply(flags.mesh)
     if flags.trans:
         V = (np.asarray(V, np.float64) @ TRANS.T).astype(np.float32)
-    scene = Scene(V, F, load_materials(flags.material))
+    if flags.inner is None:
+        scene = Scene(V, F, load_materials(flags.material))
+    else:
+        Vi, Fi = M.read_ply(flags.inner)
+        if flags.trans:
+            Vi = (np.asarray(Vi, np.float64) @ TRANS.T).astype(np.float32)
+        scene = NestedScene(V, F, load_ior(parse_ior(flags.ior), len(V)), Vi, Fi, load_materials(flags.inner_material))
     env = read_hdr(flags.hdr)
     poses = camera_in_mesh_frame(relighting_poses(flags.num, flags.azimuth, flags.elevation, flags.cam_dist))
     K = intrinsics(flags.height, flags.width, flags.focal_mm, flags.sensor_mm)
     for k in todo:
-        img = relight(scene, None, None, env, poses[k:k + 1], flags.height, flags.width, flags.samples, flags.seed, flags.chunk, K=K, img0=k)
+        if flags.inner is None:
+            img = relight(scene, None, None, env, poses[k:k + 1], flags.height, flags.width, flags.samples, flags.seed, flags.chunk, K=K, img0=k)
+        else:
+            img = relight_nested(scene, env, poses[k:k + 1], flags.height, flags.width, flags.samples, flags.seed, flags.chunk, K=K, img0=k)
         write_png(frame_path(out, k), img[0])
     print(f'wrote {len(todo)} frames to {out} ({flags.num - len(todo)} existed)')
     return out
