@@ -436,6 +436,51 @@ int nu_relight_nested_resolve(const float* inner_rows, const float* chain, const
                               float scale, int last, float* out, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Relighting through the THIN shell: the nested object of the non-zero-thickness stage-2 model.  The outer mesh
+ * is a glass wall -- per vertex an index ior [V_o] > 0, a thickness [V_o] >= 0 and a Gaussian curvature [V_o] -- around an air-like
+ * cavity (index 1.0001) that holds the opaque inner mesh.  A ray crosses the wall by the trained geometry (s2_shell_core of
+ * csrc/stage2.hip after its sigmoids: two concentric spheres of radius 1 / sqrt(max(|curvature|, 1e-6)) at the hit); each face
+ * transmits 1 - Schlick (F0 from the face's two indices, the cosine of the lower-index side); a crossing any face of which reflects
+ * totally ends the path dark.  The outer G-buffer comes from nu_relight_gbuffer with ior - 1, thickness, curvature in columns 0..2
+ * of the outer materials.  Records are those of the nested entries above, and nu_relight_nested_resolve shades them.
+ *   nu_relight_thin_chain   as nu_relight_nested_chain with ONE cavity segment (no max_segments): entry crossing, reflection ray of its
+ *                           first face (any hit, outer), the cavity ray from behind the wall (no eps) closest-hit against the inner
+ *                           and the outer tree, inner first when t_inner <= t_outer; an outer hit takes the leaving crossing and the
+ *                           exit ray (any hit, outer, origin pushed eps along the outward geometric normal).  chain [n_pix, 12] as
+ *                           above with T = keep_entry * keep_exit, keep = (1 - F_a)(1 - F_b), and F_entry = F_a of the entry crossing.
+ *   nu_relight_thin_light   as nu_relight_nested_light with the leaving crossing; rec = (exit direction, keep).
+ *   nu_relight_thin_chain_dump / _light_dump   also what they traced (tests): seg [n_pix, 16] (one segment), aux and dump as above
+ *                           (dump[11] = the crossing got out, dump[19] = keep).
+ *   nu_relight_thin_cross   tests: the crossing of M rows -- d [M,3] unit, normal [M,3] OUTWARD shading normal, x [M,3], ior,
+ *                           thickness, curvature [M], inside 0 / 1 for all rows -> refracts, tir_ok [M] bytes, nrm (oriented unit
+ *                           normal), pend (point of the first face), ns, nd (ray behind the wall; zero when !refracts) [M,3],
+ *                           fres [M,2] = F_a, F_b.
+ * --------------------------------------------------------------------------------------------------------- */
+int nu_relight_thin_chain(const void* bvh_o, int n_faces_o, const float* V_o, const int* F_o, const float* vnormals_o, const float* ior,
+    const void* bvh_i, int n_faces_i, const float* V_i, const int* F_i, const float* vnormals_i, const float* materials_i,
+    const float* thickness, const float* curvature,
+    const float* gbuf, const int* pix, int n_pix, float eps, int* kind, float* chain,
+                          float* inner_rows, hipStream_t stream);
+int nu_relight_thin_chain_dump(const void* bvh_o, int n_faces_o, const float* V_o, const int* F_o, const float* vnormals_o, const float* ior,
+    const void* bvh_i, int n_faces_i, const float* V_i, const int* F_i, const float* vnormals_i, const float* materials_i,
+    const float* thickness, const float* curvature,
+    const float* gbuf, const int* pix, int n_pix, float eps, int* kind, float* chain,
+                               float* inner_rows, float* seg, float* aux, hipStream_t stream);
+int nu_relight_thin_light(const void* bvh_o, int n_faces_o, const float* V_o, const int* F_o, const float* vnormals_o, const float* ior,
+    const void* bvh_i, int n_faces_i, const float* V_i, const int* F_i, const float* vnormals_i, const float* materials_i,
+    const float* thickness, const float* curvature,
+    const float* inner_rows, const int* sel, int n_sel, int samples, int s0, int s_count, int seed,
+                          float eps, float* rec, hipStream_t stream);
+int nu_relight_thin_light_dump(const void* bvh_o, int n_faces_o, const float* V_o, const int* F_o, const float* vnormals_o, const float* ior,
+    const void* bvh_i, int n_faces_i, const float* V_i, const int* F_i, const float* vnormals_i, const float* materials_i,
+    const float* thickness, const float* curvature,
+    const float* inner_rows, const int* sel, int n_sel, int samples, int s0, int s_count,
+                               int seed, float eps, float* rec, float* dump, hipStream_t stream);
+int nu_relight_thin_cross(const float* d, const float* normal, const float* x, const float* ior, const float* thickness,
+                          const float* curvature, int M, int inside, unsigned char* refracts, unsigned char* tir_ok, float* nrm,
+                          float* pend, float* ns, float* nd, float* fres, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Validation metrics (network/metrics.py): PSNR and SSIM of uint8 images [n, h, w, c], channel-interleaved, c in {1, 3}.
  * Pointers need no alignment.  DESIGN.md section 18 has the exactness argument and the reduction order.
  * --------------------------------------------------------------------------------------------------------- */

@@ -1089,6 +1089,278 @@ extern "C" int nu_relight_nested_light_dump(NU_NESTED_ARGS, const float* inner_r
     return nu_nested_light_launch(NU_NESTED_PASS, inner_rows, sel, n_sel, samples, s0, s_count, seed, eps, rec, dump, true, stream);
 }
 
+// ------------------------------------------------------------------------------------------------
+// relighting through the THIN shell: the nested kernels above with the wall crossing of the non-zero-thickness model
+// (nu_rlt_cross) in place of the single interface.  New kernels -- the ones above keep their registers and their bits -- of the same
+// build: one quad per pixel / sample, every walk from ONE call site of nu_walk_quad, the same stack.  A camera path has one cavity
+// segment: a crossing that fails (total reflection at any face) ends it dark.
+// ------------------------------------------------------------------------------------------------
+struct NuThinMeshes {
+    NuNestedMeshes m;
+    const float* __restrict__ thick;       // wall thickness per vertex of the outer mesh
+    const float* __restrict__ curv;        // Gaussian curvature per vertex of the outer mesh
+};
+
+// Outer G-buffer rows carry index - 1, thickness and curvature in [10], [11], [12].  Steps: the reflection ray (any hit, outer), the
+// cavity segment (closest hit, inner then outer), the exit ray (any hit, outer).  Records as relight_nested_chain_kernel writes them.
+template <bool DUMP>
+__global__ __launch_bounds__(64) void relight_thin_chain_kernel(NuThinMeshes tm, const float* __restrict__ gbuf, const int* __restrict__ pix,
+                                                                int n_pix, float eps, int* __restrict__ kind, float* __restrict__ chain,
+                                                                float* __restrict__ irow, float* __restrict__ seg, float* __restrict__ aux) {
+    __shared__ int stack[NU_WSTACK][16];
+    const NuNestedMeshes& m = tm.m;
+    const int lane = threadIdx.x & 63, sub = lane & 3, q = lane >> 2;
+    const int i = blockIdx.x * 16 + q;
+    if (i >= n_pix) return;                                 // whole quads leave together
+    const float* g = gbuf + (long long)pix[i] * NU_RL_ROW;
+    float d0[3], x0[3], ng0[3], n[3], pend[3], cur_o[3], cur_d[3], rdir[3];
+    for (int k = 0; k < 3; ++k) { d0[k] = -g[15 + k]; x0[k] = g[1 + k]; ng0[k] = g[4 + k]; }
+    float f_entry, f_b;
+    bool refr, ok;
+    nu_rlt_cross(d0, x0, g + 7, 1.0f + g[10], g[11], g[12], false, refr, ok, n, pend, cur_o, cur_d, f_entry, f_b);
+    const bool enters = refr && ok;
+    nu_rln_reflect(d0, n, rdir);
+    const bool refl_traced = f_entry > 0.0f && nu_rl_dot3(n, rdir) > 0.0f && nu_rl_dot3(ng0, rdir) > 0.0f;
+    float T = enters ? (1.0f - f_entry) * (1.0f - f_b) : 0.0f;
+    float refl_vis = 0.0f, exit_vis = 0.0f;
+    float exit_o[3] = {0.f, 0.f, 0.f}, exit_d[3] = {0.f, 0.f, 0.f};
+    int what = NU_RLN_DARK, n_walked = 0;
+    int in_found = 0, in_id = NU_MISS_INDEX;
+    float in_t = 0.0f;
+    int phase = refl_traced ? NU_RLN_PH_REFL : (enters ? NU_RLN_PH_INNER : NU_RLN_PH_DONE);
+    if (DUMP && sub == 0) {
+        float* a = aux + (long long)i * 16;
+        for (int k = 0; k < 3; ++k) { a[k] = x0[k] + eps * ng0[k]; a[3 + k] = rdir[k]; }
+        a[6] = refl_traced ? 1.0f : 0.0f; a[7] = 0.0f;
+        for (int k = 8; k < 16; ++k) a[k] = 0.0f;
+        for (int k = 0; k < 16; ++k) seg[(long long)i * 16 + k] = 0.0f;
+    }
+    while (phase != NU_RLN_PH_DONE) {
+        float o[3], d[3];
+        const bool outer = phase != NU_RLN_PH_INNER;
+        const bool any_hit = phase == NU_RLN_PH_REFL || phase == NU_RLN_PH_EXIT;
+        for (int k = 0; k < 3; ++k) {
+            o[k] = phase == NU_RLN_PH_REFL ? x0[k] + eps * ng0[k] : (phase == NU_RLN_PH_EXIT ? exit_o[k] : cur_o[k]);
+            d[k] = phase == NU_RLN_PH_REFL ? rdir[k] : (phase == NU_RLN_PH_EXIT ? exit_d[k] : cur_d[k]);
+        }
+        int found, id;
+        float t;
+        nu_walk_quad(stack, q, sub, outer ? m.bvh_o : m.bvh_i, outer ? m.Lo : m.Li, o, d, 0.0f, 1e16f, any_hit, found, id, t);
+        if (phase == NU_RLN_PH_REFL) {
+            refl_vis = found ? 0.0f : 1.0f;
+            if (DUMP && sub == 0) aux[(long long)i * 16 + 7] = found ? 1.0f : 0.0f;
+            phase = enters ? NU_RLN_PH_INNER : NU_RLN_PH_DONE;
+        } else if (phase == NU_RLN_PH_INNER) {
+            in_found = found; in_id = id; in_t = t;
+            phase = NU_RLN_PH_OUTER;
+        } else if (phase == NU_RLN_PH_OUTER) {
+            const bool ends_inner = in_found && (!found || in_t <= t);
+            n_walked = 1;
+            if (DUMP && sub == 0) {
+                float* sg = seg + (long long)i * 16;
+                for (int k = 0; k < 3; ++k) { sg[k] = cur_o[k]; sg[3 + k] = cur_d[k]; }
+                sg[6] = __int_as_float(ends_inner ? 1 : (found ? 2 : 0));
+                sg[7] = __int_as_float(ends_inner ? in_id : id);
+                sg[8] = ends_inner ? in_t : (found ? t : 0.0f);
+                sg[9] = __int_as_float(in_found); sg[10] = __int_as_float(in_id); sg[11] = in_found ? in_t : 0.0f;
+                sg[12] = __int_as_float(found); sg[13] = __int_as_float(id); sg[14] = found ? t : 0.0f;
+                sg[15] = __int_as_float(1);                                     // the segment was walked
+            }
+            if (ends_inner) {
+                float x[3], ng[3], ns[3], bary[3];
+                int vi[3];
+                nu_rl_surface(m.Vi, m.Fi, m.VNi, cur_o, cur_d, in_id, in_t, x, ng, ns, vi, bary);
+                if (sub == 0) {
+                    float* r = irow + (long long)i * NU_RL_ROW;
+                    r[0] = in_t;
+                    for (int k = 0; k < 3; ++k) { r[1 + k] = x[k]; r[4 + k] = ng[k]; r[7 + k] = ns[k]; r[15 + k] = -cur_d[k]; }
+                    for (int k = 0; k < 5; ++k)
+                        r[10 + k] = (bary[0] * m.mat[vi[0] * 5LL + k] + bary[1] * m.mat[vi[1] * 5LL + k]) + bary[2] * m.mat[vi[2] * 5LL + k];
+                    r[18] = g[18]; r[19] = g[19];
+                }
+                what = NU_RLN_INNER;
+                phase = NU_RLN_PH_DONE;
+            } else if (found) {
+                float keep;
+                const bool out = nu_rlt_leave(m.Vo, m.Fo, m.VNo, m.ior, tm.thick, tm.curv, cur_o, cur_d, id, t, eps, exit_o, exit_d, keep);
+                T = out ? T * keep : 0.0f;
+                phase = out ? NU_RLN_PH_EXIT : NU_RLN_PH_DONE;     // a crossing that fails ends the path dark
+            } else {                                        // a leaky shell: the ray leaves as it is, and nothing can shadow it
+                for (int k = 0; k < 3; ++k) { exit_o[k] = cur_o[k]; exit_d[k] = cur_d[k]; }
+                exit_vis = 1.0f;
+                what = NU_RLN_EXIT;
+                phase = NU_RLN_PH_DONE;
+            }
+        } else {
+            exit_vis = found ? 0.0f : 1.0f;
+            if (DUMP && sub == 0) {
+                float* a = aux + (long long)i * 16 + 8;
+                for (int k = 0; k < 3; ++k) { a[k] = exit_o[k]; a[3 + k] = exit_d[k]; }
+                a[6] = 1.0f; a[7] = found ? 1.0f : 0.0f;
+            }
+            what = NU_RLN_EXIT;
+            phase = NU_RLN_PH_DONE;
+        }
+    }
+    if (sub == 0) {
+        kind[i] = what;
+        float* c = chain + (long long)i * NU_RLN_CHAIN;
+        c[0] = what == NU_RLN_DARK ? 0.0f : T;
+        for (int k = 0; k < 3; ++k) { c[1 + k] = what == NU_RLN_EXIT ? exit_d[k] : 0.0f; c[5 + k] = rdir[k]; }
+        c[4] = exit_vis; c[8] = f_entry; c[9] = refl_vis;
+        c[10] = __int_as_float(n_walked); c[11] = 0.0f;
+        if (what != NU_RLN_INNER) { for (int k = 0; k < NU_RL_ROW; ++k) irow[(long long)i * NU_RL_ROW + k] = 0.0f; }
+    }
+}
+
+// Light paths of the listed inner rows, as relight_nested_light_kernel: (a) any hit against the inner tree, (b) closest hit against the
+// outer tree along the same ray and the leaving crossing, (c) any hit against the outer tree along the ray behind the wall.  Per
+// sample one 16-byte record (exit direction, keep = (1 - F_a)(1 - F_b)), or zero for a dark sample.
+template <bool DUMP>
+__global__ __launch_bounds__(64) void relight_thin_light_kernel(NuThinMeshes tm, const float* __restrict__ irow, const int* __restrict__ sel,
+                                                                int S, int s0, int s_count, int bpp, unsigned seed, float eps,
+                                                                float4* __restrict__ rec, float* __restrict__ dump) {
+    __shared__ int stack[NU_WSTACK][16];
+    const NuNestedMeshes& m = tm.m;
+    const int lane = threadIdx.x & 63, sub = lane & 3, q = lane >> 2;
+    const int i = blockIdx.x / bpp;
+    const int c = (blockIdx.x - i * bpp) * 16 + q;
+    if (c >= s_count) return;                               // whole quads leave together
+    const long long slot = (long long)i * s_count + c;
+    float o[3], d[3];
+    unsigned bits[2];
+    const bool traced = nu_relight_shadow_ray(irow + (long long)sel[i] * NU_RL_ROW, S, s0 + c, seed, eps, o, d, bits);
+    float4 out = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float keep = 1.0f;
+    float* dp = DUMP ? dump + slot * NU_RLN_LIGHT_DUMP : nullptr;
+    if (DUMP && sub == 0) {
+        for (int k = 0; k < NU_RLN_LIGHT_DUMP; ++k) dp[k] = 0.0f;
+        for (int k = 0; k < 3; ++k) { dp[k] = o[k]; dp[3 + k] = d[k]; }
+        dp[6] = traced ? 1.0f : 0.0f;
+    }
+    int phase = traced ? 0 : 3;
+    while (phase != 3) {
+        int found, id;
+        float t;
+        nu_walk_quad(stack, q, sub, phase == 0 ? m.bvh_i : m.bvh_o, phase == 0 ? m.Li : m.Lo, o, d, 0.0f, 1e16f, phase != 1, found, id, t);
+        if (phase == 0) {
+            if (DUMP && sub == 0) dp[7] = found ? 1.0f : 0.0f;
+            phase = found ? 3 : 1;
+        } else if (phase == 1) {
+            if (DUMP && sub == 0) { dp[8] = found ? 1.0f : 0.0f; dp[9] = __int_as_float(id); dp[10] = found ? t : 0.0f; }
+            if (!found) {                                   // a leaky shell: the direction leaves unrefracted
+                out = make_float4(d[0], d[1], d[2], 1.0f);
+                phase = 3;
+            } else {
+                float o2[3], d2[3];
+                const bool ok = nu_rlt_leave(m.Vo, m.Fo, m.VNo, m.ior, tm.thick, tm.curv, o, d, id, t, eps, o2, d2, keep);
+                if (DUMP && sub == 0) {
+                    dp[11] = ok ? 1.0f : 0.0f;
+                    for (int k = 0; k < 3; ++k) { dp[12 + k] = o2[k]; dp[15 + k] = d2[k]; }
+                    dp[19] = keep;
+                }
+                for (int k = 0; k < 3; ++k) { o[k] = o2[k]; d[k] = d2[k]; }
+                phase = ok ? 2 : 3;
+            }
+        } else {
+            if (DUMP && sub == 0) dp[18] = found ? 1.0f : 0.0f;
+            if (!found) out = make_float4(d[0], d[1], d[2], keep);
+            phase = 3;
+        }
+    }
+    if (sub == 0) rec[slot] = out;
+}
+
+#define NU_THIN_ARGS NU_NESTED_ARGS, const float* thickness, const float* curvature
+#define NU_THIN_PASS NU_NESTED_PASS, thickness, curvature
+static int nu_thin_meshes(NU_THIN_ARGS, NuThinMeshes& tm) {
+    if (!thickness || !curvature) return NU_ERR_ARG;
+    tm.thick = thickness; tm.curv = curvature;
+    return nu_nested_meshes(NU_NESTED_PASS, tm.m);
+}
+
+static int nu_thin_chain_launch(NU_THIN_ARGS, const float* gbuf, const int* pix, int n_pix, float eps, int* kind, float* chain,
+                                float* inner_rows, float* seg, float* aux, bool dump, hipStream_t stream) {
+    NuThinMeshes tm;
+    if (n_pix < 0 || nu_thin_meshes(NU_THIN_PASS, tm) != NU_OK) return NU_ERR_ARG;
+    if (n_pix == 0) return NU_OK;
+    if (!gbuf || !pix || !kind || !chain || !inner_rows || (dump && (!seg || !aux))) return NU_ERR_ARG;
+    const dim3 grid(nu_cdiv(n_pix, 16));
+    if (dump)
+        hipLaunchKernelGGL((relight_thin_chain_kernel<true>), grid, dim3(64), 0, stream, tm, gbuf, pix, n_pix, eps, kind, chain, inner_rows,
+                           seg, aux);
+    else
+        hipLaunchKernelGGL((relight_thin_chain_kernel<false>), grid, dim3(64), 0, stream, tm, gbuf, pix, n_pix, eps, kind, chain, inner_rows,
+                           seg, aux);
+    return nu_launch_status();
+}
+extern "C" int nu_relight_thin_chain(NU_THIN_ARGS, const float* gbuf, const int* pix, int n_pix, float eps, int* kind, float* chain,
+                                     float* inner_rows, hipStream_t stream) {
+    return nu_thin_chain_launch(NU_THIN_PASS, gbuf, pix, n_pix, eps, kind, chain, inner_rows, nullptr, nullptr, false, stream);
+}
+extern "C" int nu_relight_thin_chain_dump(NU_THIN_ARGS, const float* gbuf, const int* pix, int n_pix, float eps, int* kind, float* chain,
+                                          float* inner_rows, float* seg, float* aux, hipStream_t stream) {
+    return nu_thin_chain_launch(NU_THIN_PASS, gbuf, pix, n_pix, eps, kind, chain, inner_rows, seg, aux, true, stream);
+}
+
+static int nu_thin_light_launch(NU_THIN_ARGS, const float* inner_rows, const int* sel, int n_sel, int samples, int s0, int s_count,
+                                int seed, float eps, float* rec, float* dump, bool dumping, hipStream_t stream) {
+    NuThinMeshes tm;
+    if (n_sel < 0 || samples < 2 || (samples & 1) || s0 < 0 || s_count < 0 || s0 + s_count > samples) return NU_ERR_ARG;
+    if (nu_thin_meshes(NU_THIN_PASS, tm) != NU_OK) return NU_ERR_ARG;
+    if (n_sel == 0 || s_count == 0) return NU_OK;
+    if (!inner_rows || !sel || !rec || (dumping && !dump)) return NU_ERR_ARG;
+    const int bpp = nu_cdiv(s_count, 16);
+    const long long blocks = (long long)n_sel * bpp;
+    if (blocks > 0x7fffffffLL) return NU_ERR_ARG;         // the caller chunks over pixels / samples
+    if (dumping)
+        hipLaunchKernelGGL((relight_thin_light_kernel<true>), dim3((unsigned)blocks), dim3(64), 0, stream, tm, inner_rows, sel, samples, s0,
+                           s_count, bpp, (unsigned)seed, eps, (float4*)rec, dump);
+    else
+        hipLaunchKernelGGL((relight_thin_light_kernel<false>), dim3((unsigned)blocks), dim3(64), 0, stream, tm, inner_rows, sel, samples, s0,
+                           s_count, bpp, (unsigned)seed, eps, (float4*)rec, dump);
+    return nu_launch_status();
+}
+extern "C" int nu_relight_thin_light(NU_THIN_ARGS, const float* inner_rows, const int* sel, int n_sel, int samples, int s0, int s_count,
+                                     int seed, float eps, float* rec, hipStream_t stream) {
+    return nu_thin_light_launch(NU_THIN_PASS, inner_rows, sel, n_sel, samples, s0, s_count, seed, eps, rec, nullptr, false, stream);
+}
+extern "C" int nu_relight_thin_light_dump(NU_THIN_ARGS, const float* inner_rows, const int* sel, int n_sel, int samples, int s0, int s_count,
+                                          int seed, float eps, float* rec, float* dump, hipStream_t stream) {
+    return nu_thin_light_launch(NU_THIN_PASS, inner_rows, sel, n_sel, samples, s0, s_count, seed, eps, rec, dump, true, stream);
+}
+
+// nu_rlt_cross row by row (tests): M rows in, the crossing's outputs out
+__global__ __launch_bounds__(256) void relight_thin_cross_kernel(const float* __restrict__ d, const float* __restrict__ nraw,
+                                                                 const float* __restrict__ x, const float* __restrict__ ior,
+                                                                 const float* __restrict__ thick, const float* __restrict__ gk, int M,
+                                                                 int inside, unsigned char* __restrict__ refracts,
+                                                                 unsigned char* __restrict__ tir_ok, float* __restrict__ nrm,
+                                                                 float* __restrict__ pend, float* __restrict__ ns, float* __restrict__ nd,
+                                                                 float* __restrict__ fres) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= M) return;
+    float dd[3], nn[3], xx[3], on[3], oe[3], os[3], od[3], f_a, f_b;
+    for (int k = 0; k < 3; ++k) { dd[k] = d[r * 3LL + k]; nn[k] = nraw[r * 3LL + k]; xx[k] = x[r * 3LL + k]; }
+    bool rf, ok;
+    nu_rlt_cross(dd, xx, nn, ior[r], thick[r], gk[r], inside != 0, rf, ok, on, oe, os, od, f_a, f_b);
+    refracts[r] = rf ? 1 : 0;
+    tir_ok[r] = ok ? 1 : 0;
+    for (int k = 0; k < 3; ++k) { nrm[r * 3LL + k] = on[k]; pend[r * 3LL + k] = oe[k]; ns[r * 3LL + k] = os[k]; nd[r * 3LL + k] = od[k]; }
+    fres[r * 2LL] = f_a; fres[r * 2LL + 1] = f_b;
+}
+extern "C" int nu_relight_thin_cross(const float* d, const float* normal, const float* x, const float* ior, const float* thickness,
+                                     const float* curvature, int M, int inside, unsigned char* refracts, unsigned char* tir_ok, float* nrm,
+                                     float* pend, float* ns, float* nd, float* fres, hipStream_t stream) {
+    if (M < 0) return NU_ERR_ARG;
+    if (M == 0) return NU_OK;
+    if (!d || !normal || !x || !ior || !thickness || !curvature || !refracts || !tir_ok || !nrm || !pend || !ns || !nd || !fres)
+        return NU_ERR_ARG;
+    hipLaunchKernelGGL(relight_thin_cross_kernel, dim3(nu_cdiv(M, 256)), dim3(256), 0, stream, d, normal, x, ior, thickness, curvature, M,
+                       inside, refracts, tir_ok, nrm, pend, ns, nd, fres);
+    return nu_launch_status();
+}
+
 // brute-force closest hit on the device (same triangle test; O(N*F)): cross-check + tiny meshes
 __global__ __launch_bounds__(256) void brute_trace_kernel(const float* __restrict__ V, const int* __restrict__ F, int nf,
                                                           const float* __restrict__ rays, int N, float tmin, float tmax,

@@ -3,6 +3,9 @@
 // instantiate the traversal template there: the library is built without relocatable device code) and by relight.hip (resolve and the
 // debug entries).  ONE definition of each, compiled under the same flags with FMA contraction off, so that the ray the visibility pass
 // traces, the ray nu_relight_shadow_rays dumps and the direction nu_relight_resolve shades are the same bits.
+// Further down: the nested object (nu_rl_surface, nu_rln_interface, nu_rln_leave -- a solid glass shell, one interface) and
+// the thin shell (nu_rlt_cross, nu_rlt_leave -- the wall crossing of the non-zero-thickness stage-2 model, the geometry of
+// s2_shell_core in stage2.hip restated after its sigmoids, with a Schlick factor per face).
 #pragma once
 #include "nu_common.h"
 
@@ -198,6 +201,128 @@ static __device__ inline bool nu_rln_leave(const float* __restrict__ V, const in
     for (int k = 0; k < 3; ++k) o2[k] = refr ? x[k] - eps * ng[k] : x[k] + eps * ng[k];
     keep = 1.0f - fres;
     return refr;
+}
+
+// ---- the thin shell: the non-zero-thickness stage-2 model -- a glass wall of thickness th around an air-like cavity ----
+#define NU_RLT_CAVITY 1.0001f        // index of the cavity behind the wall (the trained model's inner medium is 1 / 1.0001)
+
+// Schlick reflectance of one face between the media of index n_in (cosine c_in on that side) and n_out (cosine c_out): F0 =
+// ((n_in - n_out) / (n_in + n_out))^2, the cosine of the LOWER-index side (so the factor does not depend on the direction of travel),
+// F0 = 0 -> 0.  The trained geometry does not orient its normals by the ray, so a cosine may be negative: 1 - c is clamped to [0, 1].
+static __device__ inline float nu_rlt_schlick(float n_in, float n_out, float c_in, float c_out) {
+    const float r = (n_in - n_out) / (n_in + n_out), f0 = r * r;
+    const float m = fminf(fmaxf(1.0f - (n_in <= n_out ? c_in : c_out), 0.0f), 1.0f);
+    return f0 > 0.0f ? f0 + (1.0f - f0) * ((m * m) * (m * m) * m) : 0.0f;
+}
+// x / (|x| + 1e-4), as the trained model normalises
+static __device__ inline void nu_rlt_unit_eps(float* x) {
+    const float inv = 1.0f / (sqrtf(nu_rl_dot3(x, x)) + 0.0001f);
+    for (int k = 0; k < 3; ++k) x[k] = x[k] * inv;
+}
+
+// The crossing of the wall by direction d (unit) at the mesh point x: s2_shell_core<float> of stage2.hip after its two sigmoids, operation
+// for operation (r = 1 / n_g, inner medium 1 / 1.0001, th as given), compiled here without FMA contraction.  nraw = the OUTWARD shading
+// normal (any length; flipped when inside), n_g the glass index, th the wall thickness, gk the Gaussian curvature: the wall at x is two
+// concentric spheres of radius R = 1 / sqrt(max(|gk|, 1e-6)), th apart.  inside = false: air -> glass at x -> cavity; inside = true:
+// cavity -> glass at the inner sphere (the step back from x) -> air.  Outputs: refracts (the first test, eta^2 sin^2_i <= 0.999 with the
+// mesh normal), tir_ok (no later face reflects totally either), nrm = the oriented unit normal at x, pend = the point of the first
+// face, (ns, nd) = the ray behind the wall (zero when !refracts), f_a / f_b = Schlick of the first / second face (nu_rlt_schlick;
+// !refracts: f_a = 1, or 0 for index-matched media, f_b = 0).  A path goes on only when refracts && tir_ok.
+static __device__ inline void nu_rlt_cross(const float* d, const float* x, const float* nraw, float n_g, float th, float gk, bool inside,
+                                          bool& refracts, bool& tir_ok, float* nrm, float* pend, float* ns, float* nd, float& f_a,
+                                          float& f_b) {
+    {
+        const float inv = 1.0f / fmaxf(sqrtf(nu_rl_dot3(nraw, nraw)), 1e-12f);
+        for (int k = 0; k < 3; ++k) nrm[k] = inside ? -(nraw[k] * inv) : nraw[k] * inv;
+    }
+    float r = 1.0f / n_g;
+    const float inner = 1.0f / 1.0001f;
+    float ro = inner / r;
+    if (inside) { const float tmp = r; r = 1.0f / ro; ro = 1.0f / tmp; }
+    const float n_first_in = inside ? NU_RLT_CAVITY : 1.0f, n_last_out = inside ? 1.0f : NU_RLT_CAVITY;
+    const float cos_i = -nu_rl_dot3(nrm, d);
+    const float sin2_i = 1.0f - cos_i * cos_i;
+    refracts = !(r * r * sin2_i > 0.999f);
+    tir_ok = refracts;
+    for (int k = 0; k < 3; ++k) { pend[k] = x[k]; ns[k] = 0.0f; nd[k] = 0.0f; }
+    f_b = 0.0f;
+    if (!refracts) {
+        const float q = (n_first_in - n_g) / (n_first_in + n_g);
+        f_a = q * q > 0.0f ? 1.0f : 0.0f;
+        return;
+    }
+    const float sin2_t = sin2_i * r * r;
+    float R = 1.0f / sqrtf(fmaxf(fabsf(gk), 0.000001f));
+    if (R != R) R = 0.1f;
+    const float cos_t = sqrtf(fmaxf(1.0f - sin2_t, 0.0001f));
+    const bool positive = inside ? (gk <= 0.0f) : (gk >= 0.0f);
+    const float two_R_th = R * th * 2.0f, th2 = th * th;
+    float pm[3], nm[3], din[3];
+    if (!inside) {
+        const float f = r * cos_i - cos_t;
+        for (int k = 0; k < 3; ++k) { din[k] = r * d[k] + f * nrm[k]; pm[k] = x[k]; nm[k] = nrm[k]; }
+        nu_rlt_unit_eps(din);
+        f_a = nu_rlt_schlick(n_first_in, n_g, cos_i, cos_t);
+    } else {
+        const float ci = R * cos_i;
+        const float delta2 = positive ? (ci * ci - two_R_th + th2) : (ci * ci + two_R_th + th2);
+        const float len = fabsf(ci - sqrtf(fmaxf(delta2, 0.0001f)));
+        for (int k = 0; k < 3; ++k) {
+            const float center = positive ? (x[k] - nrm[k] * R) : (x[k] + nrm[k] * R);
+            pm[k] = x[k] - len * d[k];
+            nm[k] = positive ? (pm[k] - center) : (center - pm[k]);
+            pend[k] = pm[k];
+        }
+        nu_rlt_unit_eps(nm);
+        const float cos_im = -nu_rl_dot3(nm, d);
+        const float xx = (1.0f - cos_im * cos_im) * r * r;
+        if (xx > 0.999f) tir_ok = false;
+        const float cos_tm = sqrtf(fmaxf(1.0f - fminf(xx, 0.999f), 0.0001f));
+        const float f = r * cos_im - cos_tm;
+        for (int k = 0; k < 3; ++k) din[k] = r * d[k] + f * nm[k];
+        nu_rlt_unit_eps(din);
+        f_a = nu_rlt_schlick(n_first_in, n_g, cos_im, cos_tm);
+    }
+    // the chord through the wall and the second face
+    const float cr = R * cos_t;
+    const float delta2 = positive ? (cr * cr - two_R_th + th2) : (cr * cr + two_R_th + th2);
+    const float len = fabsf(cr - sqrtf(fmaxf(delta2, 0.0001f))) + 0.001f;
+    float na[3];
+    for (int k = 0; k < 3; ++k) {
+        const float center = positive ? (pm[k] - nm[k] * R) : (pm[k] + nm[k] * R);
+        ns[k] = pm[k] + din[k] * len;
+        na[k] = positive ? (ns[k] - center) : (center - ns[k]);
+    }
+    nu_rlt_unit_eps(na);
+    const float cos_i2 = -nu_rl_dot3(na, din);
+    const float x2 = (1.0f - cos_i2 * cos_i2) * ro * ro;
+    if (x2 > 0.999f) tir_ok = false;
+    const float cos_t2 = sqrtf(fmaxf(1.0f - fminf(x2, 0.999f), 0.0001f));
+    const float f2 = ro * cos_i2 - cos_t2;
+    for (int k = 0; k < 3; ++k) nd[k] = ro * din[k] + f2 * na[k];
+    nu_rlt_unit_eps(nd);
+    f_b = nu_rlt_schlick(n_g, n_last_out, cos_i2, cos_t2);
+}
+
+// A ray (o, d) of the cavity met face `id` of the outer mesh at distance t: the leaving crossing with index, thickness and curvature
+// interpolated from the per-vertex arrays by the barycentrics of the hit (the index as 1 + sum w (n - 1), like the primary hit).  Returns
+// true when the ray gets out: (o2, d2) = the ray behind the wall, its origin pushed eps along the OUTWARD geometric normal, and
+// keep = (1 - F_a)(1 - F_b).  Returns false when any face reflects totally: the path is dark (no interior bounce is modelled).
+static __device__ inline bool nu_rlt_leave(const float* __restrict__ V, const int* __restrict__ F, const float* __restrict__ VN,
+                                          const float* __restrict__ ior, const float* __restrict__ thick, const float* __restrict__ curv,
+                                          const float* o, const float* d, int id, float t, float eps, float* o2, float* d2, float& keep) {
+    float x[3], ng[3], nsh[3], bary[3], nout[3], nrm[3], pend[3], f_a, f_b;
+    int vi[3];
+    nu_rl_surface(V, F, VN, o, d, id, t, x, ng, nsh, vi, bary);
+    const float index = 1.0f + ((bary[0] * (ior[vi[0]] - 1.0f) + bary[1] * (ior[vi[1]] - 1.0f)) + bary[2] * (ior[vi[2]] - 1.0f));
+    const float th = (bary[0] * thick[vi[0]] + bary[1] * thick[vi[1]]) + bary[2] * thick[vi[2]];
+    const float gk = (bary[0] * curv[vi[0]] + bary[1] * curv[vi[1]]) + bary[2] * curv[vi[2]];
+    for (int k = 0; k < 3; ++k) nout[k] = -nsh[k];           // nu_rl_surface's shading normal faces the ray: the outward one is its negative
+    bool refr, ok;
+    nu_rlt_cross(d, x, nout, index, th, gk, true, refr, ok, nrm, pend, o2, d2, f_a, f_b);
+    for (int k = 0; k < 3; ++k) o2[k] = o2[k] - eps * ng[k];
+    keep = (1.0f - f_a) * (1.0f - f_b);
+    return refr && ok;
 }
 
 // Lat-long environment, z up: column u = (1/2 - atan2(d.y, d.x) / 2 pi) * W, row v = atan2(hypot(d.x, d.y), d.z) / pi * H (row 0 = +z);

@@ -10,7 +10,8 @@ data/materials/{name}-{step}.  --stage2: a stage-2 config; --inner (default) bak
 the stage-2 model carries; both also write DIR/ior.npy [V_outer,1], the learned index of refraction at the vertices of the outer
 shell (materials.predict_ior) that relight --ior DIR takes.  With --inner the shell is the stage-1 mesh of the config
 (stage1_mesh_dir), NOT --mesh: ior.npy is in that file's vertex order, and that same file is what relight --mesh must be given
-(relight checks the vertex count only).  --ply also writes DIR/{mesh stem}_albedo.ply: the mesh with the albedo as uint8 vertex colours.
+(relight checks the vertex count only).  A `zero_thickness: false` config (the thin-shell model) additionally gets DIR/shell_ior.npy
+and DIR/shell_thickness.npy [V_outer,1] (materials.predict_shell), the directory relight --shell DIR takes.  --ply also writes DIR/{mesh stem}_albedo.ply: the mesh with the albedo as uint8 vertex colours.
 """
 import argparse
 import os
@@ -63,6 +64,16 @@ def save_ior(out, ior):
     return os.path.join(out, 'ior.npy')
 
 
+def save_shell(out, shell):
+    """DIR/shell_ior.npy, DIR/shell_thickness.npy [V,1] float32: what relight --shell DIR reads."""
+    import numpy as np
+    paths = []
+    for k in ('ior', 'thickness'):
+        paths.append(os.path.join(out, f'shell_{k}.npy'))
+        np.save(paths[-1], np.ascontiguousarray(shell[k], np.float32).reshape(-1, 1))
+    return paths
+
+
 def main(argv=None):
     flags = parse_args(argv)
     import numpy as np
@@ -70,7 +81,7 @@ def main(argv=None):
     import yaml
     from . import mesh as M
     from .extract_mesh import _renderer
-    from .materials import predict_ior, predict_materials
+    from .materials import is_thick_stage2, predict_ior, predict_materials, predict_shell
     from .train_glue import load_checkpoint
 
     with open(flags.cfg) as fh:
@@ -96,8 +107,12 @@ def main(argv=None):
         np.save(os.path.join(out, k + '.npy'), mats[k].astype(np.float32))
     print(f'wrote {out}/metallic.npy, roughness.npy, albedo.npy: {len(V)} vertices of {mesh_path}')
     if flags.stage2:
-        save_ior(out, predict_ior(network, ior_mesh(flags, network, (V, F))))
+        shell_mesh = ior_mesh(flags, network, (V, F))
+        save_ior(out, predict_ior(network, shell_mesh))
         print(f'wrote {out}/ior.npy')
+        if is_thick_stage2(network):                         # the non-zero-thickness model: the shell relight --shell takes
+            save_shell(out, predict_shell(network, shell_mesh))
+            print(f'wrote {out}/shell_ior.npy, shell_thickness.npy')
     if ply_path:
         M.write_ply(ply_path, V, F, colors=mats['albedo'])
         print(f'wrote {ply_path}')

@@ -128,3 +128,33 @@ def predict_ior(renderer, mesh=None):
         return np.zeros((0, 1), np.float32)
     raw = torch.sigmoid(renderer.nets()[1].ior(G.embed(x, 6)))
     return (raw.reshape(-1, 1) * 1.0 + 1.0).cpu().numpy().astype(np.float32)
+
+
+def is_thick_stage2(renderer):
+    """True for the non-zero-thickness stage-2 renderer (the zero-thickness class carries an unused thickness network too, so the
+    class decides)."""
+    from .stage2_thick import Stage2Renderer
+    return isinstance(renderer, Stage2Renderer)
+
+
+@torch.no_grad()
+def predict_shell(renderer, mesh=None):
+    """The shell of the NON-zero-thickness stage-2 model (stage2_thick.Stage2Renderer) at the vertices of the OUTER mesh, in the vertex
+    order of `mesh` (as mesh_vertices reads it): {'ior' [V,1], 'thickness' [V,1]} float32 numpy.  The two networks exactly as
+    stage2_thick.trace_segments evaluates them (nets.ior_and_thickness on the 6-frequency embedding of the point) and the mapping of
+    the crossing (s2_shell_core): glass index = sigmoid(raw) + 0.6 in (0.6, 1.6), wall thickness = 0.01 * sigmoid(raw).  This is what
+    relight --shell takes; predict_ior stays the zero-thickness formula."""
+    if not is_thick_stage2(renderer):
+        raise ValueError("predict_shell: only the non-zero-thickness stage-2 renderer has a shell of learned index and thickness")
+    from . import torch_glue as G
+    V = mesh_vertices(renderer, mesh)
+    dev = next(renderer.parameters()).device
+    x = torch.from_numpy(V).to(dev)
+    if x.shape[0] == 0:
+        return {'ior': np.zeros((0, 1), np.float32), 'thickness': np.zeros((0, 1), np.float32)}
+    inner = renderer.nets()[1]
+    inner.eng.pack()                   # the packed weight tables the GEMMs read, as every render pass refreshes them first
+    ior_raw, thick_raw = inner.ior_and_thickness(G.embed(x, 6))
+    ior = torch.sigmoid(ior_raw).reshape(-1, 1) * 1.0 + 0.6
+    thickness = torch.sigmoid(thick_raw).reshape(-1, 1) * 0.01
+    return {'ior': ior.cpu().numpy().astype(np.float32), 'thickness': thickness.cpu().numpy().astype(np.float32)}

@@ -1,5 +1,5 @@
 """python -m nu_nerf_amd.relight --mesh PLY --material DIR --hdr FILE --name NAME [--trans] [--num 360 --width 800 --height 800
---samples 1024 --cam_dist 3.0 --azimuth 0 --elevation 45] [--inner PLY --inner-material DIR --ior VALUE_OR_DIR]
+--samples 1024 --cam_dist 3.0 --azimuth 0 --elevation 45] [--inner PLY --inner-material DIR (--ior VALUE_OR_DIR | --shell DIR_OR_PAIR)]
 
 relight.py + blender_backend/relight_backend.py on the GPU: the extracted mesh, the per-vertex DIR/metallic.npy, roughness.npy and
 albedo.npy that extract_materials writes and a lat-long HDR environment map are rendered from the reference's camera orbit
@@ -12,7 +12,9 @@ against Blender output.
 --inner: the nested object of stage 2.  --mesh is then the transparent outer shell, --inner the cleaned inner mesh with its baked
 --inner-material, --ior the shell's index of refraction: a number (default 1.5) or the directory whose ior.npy [V,1]
 extract_materials --stage2 wrote; --material is not needed.  The view refracts into the shell, the inner object is lit through it
-(DESIGN.md 21).  --trans turns both meshes.
+(DESIGN.md 21).  --trans turns both meshes.  --shell instead of --ior: the shell is the thin glass wall of the non-zero-thickness
+stage-2 model around an air-like cavity: the directory whose shell_ior.npy and shell_thickness.npy [V,1]
+extract_materials --stage2 wrote for such a config, or "IOR,THICKNESS" (two numbers, e.g. "1.45,0.005").
 
 --hdr takes a Radiance .hdr (RGBE, flat or run-length scanlines) or a .npy float [H,W,3]; the map is z up in the mesh's frame.
 --focal_mm / --sensor_mm: Blender's default camera (50 mm on a 36 mm sensor fitted to the larger image side).  --seed, --chunk
@@ -385,9 +387,109 @@ def nested_resolve(irow, chain, kind, opix, sel, samples, s0, s_count, seed, env
     return out
 
 
+# ---- the thin shell ---------------------------------------------------------------------------------------------------
+def _per_vertex(value, nv, what):
+    import torch
+    a = np.asarray(value.cpu() if torch.is_tensor(value) else value, np.float32)
+    a = np.full(nv, float(a), np.float32) if a.ndim == 0 else a.reshape(-1)
+    if a.shape != (nv,):
+        raise ValueError(f"{what} must be a scalar or give one value for each of the {nv} outer vertices, got {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+class ThinShellScene:
+    """The nested object of the non-zero-thickness stage-2 model: the outer mesh is a glass wall with a per-vertex index `ior` (finite,
+    > 0; the trained range is 0.6 .. 1.6) and `thickness` (finite, >= 0; trained 0 .. 0.01) around an air-like cavity with the opaque
+    inner mesh.  Scalars or [V_o] / [V_o,1].  curvature: the per-vertex Gaussian curvature the wall's two spheres take their radius
+    from; default lbvh.vertex_normals_and_curvature of the outer mesh (angle defect over vertex area, clipped to +-10: what the
+    stage-2 model trains with).  The outer Scene's material table holds index - 1, thickness and curvature in columns 0..2, so that the
+    G-buffer pass interpolates them with the barycentrics of the primary hit."""
+
+    def __init__(self, V_o, F_o, ior, thickness, V_i, F_i, materials_i, curvature=None, device=None):
+        import torch
+        from .lbvh import vertex_normals_and_curvature
+        nv = int(V_o.shape[0])
+        ior, thickness = _per_vertex(ior, nv, 'ior'), _per_vertex(thickness, nv, 'thickness')
+        if not np.isfinite(ior).all() or (ior <= 0.0).any():
+            raise ValueError("ior must be finite and > 0")
+        if not np.isfinite(thickness).all() or (thickness < 0.0).any():
+            raise ValueError("thickness must be finite and >= 0")
+        if curvature is None:
+            Vt = torch.as_tensor(np.asarray(V_o) if not torch.is_tensor(V_o) else V_o).detach().cpu().to(torch.float32)
+            Ft = torch.as_tensor(np.asarray(F_o) if not torch.is_tensor(F_o) else F_o).detach().cpu().to(torch.long)
+            curvature = vertex_normals_and_curvature(Vt, Ft)[1]       # clipped to [-10, 10] there, as the stage-2 model trains with it
+        curvature = _per_vertex(curvature, nv, 'curvature')
+        if not np.isfinite(curvature).all():
+            raise ValueError("curvature must be finite")
+        mo = np.zeros((nv, 5), np.float32)
+        mo[:, 0], mo[:, 1], mo[:, 2] = ior - 1.0, thickness, curvature
+        self.outer = Scene(V_o, F_o, mo, device)
+        self.inner = Scene(V_i, F_i, materials_i, self.outer.device)
+        self.device = self.outer.device
+        self.ior = torch.from_numpy(ior).to(self.device)
+        self.thickness = torch.from_numpy(thickness).to(self.device)
+        self.curvature = torch.from_numpy(curvature).to(self.device)
+
+    def _args(self):
+        from . import _lib as L
+        return NestedScene._args(self) + (L.ptr(self.thickness), L.ptr(self.curvature))
+
+
+def thin_chain(ts, gbuf, pix, eps=ORIGIN_EPS, dump=False):
+    """nested_chain for a ThinShellScene (one cavity segment): kind int32 [n], chain float32 [n, CHAIN], inner rows float32 [n, ROW];
+    with dump also seg [n, SEG] and aux [n, 2, 8]."""
+    import torch
+    from . import _lib as L
+    n = int(pix.shape[0])
+    kind = torch.empty(n, dtype=torch.int32, device=ts.device)
+    chain = torch.empty(n, CHAIN, dtype=torch.float32, device=ts.device)
+    irow = torch.empty(n, ROW, dtype=torch.float32, device=ts.device)
+    if not dump:
+        L.load().nu_relight_thin_chain(*ts._args(), L.ptr(gbuf), L.ptr(pix), n, float(eps), L.ptr(kind), L.ptr(chain), L.ptr(irow), L.stream())
+        return kind, chain, irow
+    seg = torch.empty(n, SEG, dtype=torch.float32, device=ts.device)
+    aux = torch.empty(n, 2, 8, dtype=torch.float32, device=ts.device)
+    L.load().nu_relight_thin_chain_dump(*ts._args(), L.ptr(gbuf), L.ptr(pix), n, float(eps), L.ptr(kind), L.ptr(chain), L.ptr(irow),
+                                        L.ptr(seg), L.ptr(aux), L.stream())
+    return kind, chain, irow, seg, aux
+
+
+def thin_light(ts, irow, sel, samples, s0, s_count, seed, eps=ORIGIN_EPS, dump=False):
+    """nested_light for a ThinShellScene: rec float32 [n_sel, s_count, 4] = (exit direction, keep of the leaving crossing), zero where
+    the sample is dark; with dump also [n_sel * s_count, LIGHT_DUMP]."""
+    import torch
+    from . import _lib as L
+    n = int(sel.shape[0])
+    rec = torch.empty(n, int(s_count), 4, dtype=torch.float32, device=ts.device)
+    if not dump:
+        L.load().nu_relight_thin_light(*ts._args(), L.ptr(irow), L.ptr(sel), n, int(samples), int(s0), int(s_count), _seed(seed), float(eps),
+                                       L.ptr(rec), L.stream())
+        return rec
+    d = torch.empty(n * int(s_count), LIGHT_DUMP, dtype=torch.float32, device=ts.device)
+    L.load().nu_relight_thin_light_dump(*ts._args(), L.ptr(irow), L.ptr(sel), n, int(samples), int(s0), int(s_count), _seed(seed),
+                                        float(eps), L.ptr(rec), L.ptr(d), L.stream())
+    return rec, d
+
+
+def thin_cross(d, normal, x, ior, thickness, curvature, inside):
+    """The wall crossing row by row (tests): d, normal (outward), x [M,3], ior, thickness, curvature [M] float32 device tensors ->
+    dict(refracts, tir_ok [M] bool, normal, end, next_start, next_dir [M,3], fresnel [M,2] = F of the first and the second face)."""
+    import torch
+    from . import _lib as L
+    M = int(d.shape[0])
+    ins = [t.to(torch.float32).contiguous() for t in (d, normal, x, ior, thickness, curvature)]
+    e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=d.device)      # noqa: E731
+    refr, ok = e(M, dt=torch.uint8), e(M, dt=torch.uint8)
+    nrm, pend, ns, nd, fres = e(M, 3), e(M, 3), e(M, 3), e(M, 3), e(M, 2)
+    L.load().nu_relight_thin_cross(*[L.ptr(t) for t in ins], M, 1 if inside else 0, L.ptr(refr), L.ptr(ok), L.ptr(nrm), L.ptr(pend),
+                                   L.ptr(ns), L.ptr(nd), L.ptr(fres), L.stream())
+    return dict(refracts=refr != 0, tir_ok=ok != 0, normal=nrm, end=pend, next_start=ns, next_dir=nd, fresnel=fres)
+
+
 def relight_nested_linear(scene, env, poses, h, w, samples, seed=0, chunk=256, rows=None, images=1, K=None, img0=0, eps=ORIGIN_EPS,
                           max_segments=MAX_SEGMENTS):
-    """relight_linear for a NestedScene: linear radiance float32 [n,h,w,4], alpha 1 where the primary ray hits the OUTER mesh.  The same
+    """relight_linear for a NestedScene or a ThinShellScene (the scene's type picks the shell's transport; max_segments applies to a
+    NestedScene only): linear radiance float32 [n,h,w,4], alpha 1 where the primary ray hits the OUTER mesh.  The same
     piece / sample chunking with the same guarantee: the result does not depend on `images`, `rows` or `chunk`, bit for bit.  Device
     memory besides the meshes, the environment and the result: 232 bytes per pixel of a piece (outer row, face id, hit list, chain
     record, kind, inner row) plus at most VIS_BYTES of 16-byte sample records."""
@@ -398,6 +500,7 @@ def relight_nested_linear(scene, env, poses, h, w, samples, seed=0, chunk=256, r
         raise ValueError(f"samples must be even and >= 2, got {samples}")
     if chunk < 1 or images < 1 or (rows is not None and rows < 1):
         raise ValueError("chunk, rows and images must be >= 1")
+    thin = isinstance(scene, ThinShellScene)
     dev = scene.device
     poses = np.asarray(poses.cpu() if torch.is_tensor(poses) else poses, np.float64).reshape(-1, 3, 4)
     K = intrinsics(h, w) if K is None else np.asarray(K, np.float64)
@@ -414,7 +517,7 @@ def relight_nested_linear(scene, env, poses, h, w, samples, seed=0, chunk=256, r
             face, gbuf = gbuffer(scene.outer, cams[i0:i0 + ni], h, w, img0 + i0, y0, nr)
             pix = hit_pixels(face)
             piece = torch.zeros(ni * nr * w, 4, dtype=torch.float32, device=dev)
-            kind, chain, irow = nested_chain(scene, gbuf, pix, eps, max_segments)
+            kind, chain, irow = thin_chain(scene, gbuf, pix, eps) if thin else nested_chain(scene, gbuf, pix, eps, max_segments)
             inner = (kind == INNER).nonzero().flatten().to(torch.int32)
             other = (kind != INNER).nonzero().flatten().to(torch.int32)
             nested_resolve(irow, chain, kind, pix, other, samples, 0, 0, seed, envd, None, True, piece)
@@ -422,7 +525,7 @@ def relight_nested_linear(scene, env, poses, h, w, samples, seed=0, chunk=256, r
                 sel = inner[p0:p0 + per].contiguous()
                 for s0 in range(0, samples, chunk):
                     sc = min(chunk, samples - s0)
-                    rec = nested_light(scene, irow, sel, samples, s0, sc, seed, eps)
+                    rec = (thin_light if thin else nested_light)(scene, irow, sel, samples, s0, sc, seed, eps)
                     nested_resolve(irow, chain, kind, pix, sel, samples, s0, sc, seed, envd, rec, s0 + sc == samples, piece)
             out[i0:i0 + ni, y0:y0 + nr] = piece.reshape(ni, nr, w, 4)
     return out
@@ -457,7 +560,10 @@ def parse_args(argv=None):
     ap.add_argument('--trans', action='store_true', default=False, help="turn the mesh +90 degrees about x")
     ap.add_argument('--inner', type=str, default=None, help="inner mesh (PLY): --mesh is then the transparent shell around it")
     ap.add_argument('--inner-material', dest='inner_material', type=str, default=None, help="material directory of the inner mesh")
-    ap.add_argument('--ior', type=str, default='1.5', help="index of refraction of the shell: a number or a directory with ior.npy [V,1]")
+    ap.add_argument('--ior', type=str, default=None,
+                    help="index of refraction of the shell: a number (default 1.5) or a directory with ior.npy [V,1]")
+    ap.add_argument('--shell', type=str, default=None,
+                    help="thin glass shell instead of --ior: a directory with shell_ior.npy and shell_thickness.npy [V,1], or \"IOR,THICKNESS\"")
     ap.add_argument('--output', type=str, default=None, help="output directory (default data/relight/NAME)")
     ap.add_argument('--width', type=int, default=800)
     ap.add_argument('--height', type=int, default=800)
@@ -475,14 +581,23 @@ def parse_args(argv=None):
         ap.error("--samples must be even and >= 2")
     if flags.num < 1 or flags.width < 1 or flags.height < 1 or flags.chunk < 1:
         ap.error("--num, --width, --height and --chunk must be >= 1")
+    if flags.shell is not None and flags.ior is not None:
+        ap.error("--shell and --ior exclude each other: the shell is either the thin wall or solid glass")
+    if flags.ior is None:
+        flags.ior = '1.5'
     if flags.inner is None:
         if flags.inner_material is not None:
             ap.error("--inner-material needs --inner")
+        if flags.shell is not None:
+            ap.error("--shell needs --inner")
     else:
         if flags.inner_material is None:
             ap.error("--inner needs --inner-material")
         try:
-            parse_ior(flags.ior)
+            if flags.shell is not None:
+                parse_shell(flags.shell)
+            else:
+                parse_ior(flags.ior)
         except ValueError as e:
             ap.error(str(e))
     return flags
@@ -507,6 +622,26 @@ def load_ior(spec, n_verts):
     if a.size != n_verts or a.shape not in ((n_verts,), (n_verts, 1)):
         raise ValueError(f"{spec}: expected [{n_verts},1] (one index of refraction per vertex of the shell), got {a.shape}")
     return np.ascontiguousarray(a, np.float32).reshape(-1)
+
+
+def parse_shell(text):
+    """--shell: "IOR,THICKNESS" (index > 0, thickness >= 0) -> (float, float); anything else -> the paths (DIR/shell_ior.npy,
+    DIR/shell_thickness.npy) of a directory as extract_materials writes it."""
+    parts = text.split(',')
+    try:
+        values = [float(p) for p in parts]
+    except ValueError:
+        return os.path.join(text, 'shell_ior.npy'), os.path.join(text, 'shell_thickness.npy')
+    if len(values) != 2:
+        raise ValueError(f"--shell takes a directory or two numbers IOR,THICKNESS, got {text}")
+    if not np.isfinite(values).all() or values[0] <= 0.0 or values[1] < 0.0:
+        raise ValueError(f"--shell needs IOR > 0 and THICKNESS >= 0, got {text}")
+    return values[0], values[1]
+
+
+def load_shell(spec, n_verts):
+    """(ior, thickness) float32 [n_verts] each from what parse_shell returns."""
+    return tuple(load_ior(v, n_verts) for v in spec)
 
 
 def output_dir(flags):
@@ -544,7 +679,11 @@ def main(argv=None):
         Vi, Fi = M.read_ply(flags.inner)
         if flags.trans:
             Vi = (np.asarray(Vi, np.float64) @ TRANS.T).astype(np.float32)
-        scene = NestedScene(V, F, load_ior(parse_ior(flags.ior), len(V)), Vi, Fi, load_materials(flags.inner_material))
+        if flags.shell is not None:
+            ior, thickness = load_shell(parse_shell(flags.shell), len(V))
+            scene = ThinShellScene(V, F, ior, thickness, Vi, Fi, load_materials(flags.inner_material))
+        else:
+            scene = NestedScene(V, F, load_ior(parse_ior(flags.ior), len(V)), Vi, Fi, load_materials(flags.inner_material))
     env = read_hdr(flags.hdr)
     poses = camera_in_mesh_frame(relighting_poses(flags.num, flags.azimuth, flags.elevation, flags.cam_dist))
     K = intrinsics(flags.height, flags.width, flags.focal_mm, flags.sensor_mm)
