@@ -442,20 +442,9 @@ def test_shade_encode_kernels_vs_float64(gpu, sphere, pos_freq, rf):
     OL, IL, IW, RL, nov, SD = O.shade_encode(eng, *ins, sphere, pos_freq, rf)
     # ---- float64 reference ----
     xd, nd, vd, md = (t.double().requires_grad_(True) for t in (x, nrm, view, m_raw))
-    from oracle.stage1_oracle import _IDE_ML, _IDE_MAT        # (m, l) list and coefficient matrix of the IDE (ref_utils.py:7-79)
-    mt, lt, mat = torch.from_numpy(_IDE_ML[:, 0]).long(), torch.from_numpy(_IDE_ML[:, 1]), torch.from_numpy(_IDE_MAT)
-
-    def ide64(d, kinv):
-        xx, yy, zz = d[..., 0:1], d[..., 1:2], d[..., 2:3]
-        zp = torch.cat([torch.ones_like(zz)] + [zz ** i for i in range(1, 17)], -1)
-        re, im = [torch.ones_like(xx)], [torch.zeros_like(xx)]
-        for _ in range(16):
-            re.append(re[-1] * xx - im[-1] * yy)
-            im.append(re[-2] * yy + im[-1] * xx)
-        re, im = torch.cat(re, -1)[..., mt], torch.cat(im, -1)[..., mt]
-        att = torch.exp(-0.5 * lt.double() * (lt.double() + 1) * kinv)
-        poly = zp @ mat.double()
-        return torch.cat([re * poly * att, im * poly * att], -1)
+    from oracle.stage1_oracle import _IDE_MAT                 # coefficient matrix of the IDE (ref_utils.py:7-79)
+    from encode_oracle import ide64                           # the float64 IDE (shared with tests/test_encode_ops_gpu.py)
+    mat = torch.from_numpy(_IDE_MAT)
     n, v = F.normalize(nd, dim=-1), F.normalize(vd, dim=-1)
     nov_r = torch.sum(n * v, -1, keepdim=True)
     refl = nov_r * n * 2 - v
