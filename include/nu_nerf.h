@@ -864,6 +864,62 @@ int nu_rm_relax(NU_RM_ARGS, float* Vout, hipStream_t stream);
 int nu_rm_project(const float* V, int nv, const unsigned char* vlock, const float* closest, float* Vout, hipStream_t stream);
 #undef NU_RM_ARGS
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Mesh components: labelling, per-component statistics and compaction (csrc/components.hip; the driver nu_nerf_amd/components.py
+ * sorts and scans between the entries, as remesh.py does).  Every buffer is the caller's, every launch goes on `stream`.
+ * Labelling is hook-and-compress over links[nl,2] (int32 node pairs; a pair (x, x) is no link) on parent[n] (int32):
+ *   nu_cc_init             parent[x] = x
+ *   nu_cc_vertex_links     nodes = vertices: links[2 nf, 2] = (v0, v1), (v1, v2) of every face
+ *   nu_cc_edge_links       nodes = faces: links[nh, 2] from the STABLY sorted nu_rm_edge_keys and their permutation (int64): slot i
+ *                          joins the faces of slots i - 1 and i when their keys are equal (an edge of k faces chains all k)
+ *   nu_cc_hook             per link: the roots ra, rb of its nodes; atomicMin(parent[max(ra, rb)], min(ra, rb)).  parent[x] <= x
+ *                          always, so every walk decreases and ends; a stale read is an ancestor of the same component
+ *   nu_cc_compress         parent[x] = root of x
+ *   nu_cc_check            flag[0] (int32, zeroed here) = 1 when a link still joins two roots (parent[a] != parent[b])
+ * One round = hook, compress, check; the driver reads flag once per round and stops at the first clean one.  The fixed point is the
+ * smallest node id of each component, whatever the arrival order.
+ *   nu_cc_mark_used        used[nv] int32 (zeroed here) = 1 at every vertex a face references
+ *   nu_cc_root_flags       isroot[n] int32 = parent[x] == x and (used == NULL or used[x])
+ *   nu_cc_labels           rinc = inclusive int64 scan of isroot: label[x] = rinc[parent[x]] - 1 (-1 where used[x] == 0): component
+ *                          ids 0 .. C-1 ascend with the smallest node id
+ *   nu_cc_face_labels      flabel[f] = vlabel[F[f][0]]
+ *   nu_cc_keep_flags       fkeep[f] = keep_comp[flabel[f]] (int32 [C]); vkeep[nv] (zeroed here) = 1 at the vertices of kept faces
+ *   nu_cc_compact          finc / vinc = inclusive int64 scans of fkeep / vkeep: kept vertices and faces in their order, indices
+ *                          rewritten (Vout [vinc[nv-1], 3], Fout [finc[nf-1], 3])
+ * Statistics of the components of flabel[nf] in [0, C):
+ *   nu_cc_face_stats       order[nf] (int64) = the stable sort of the faces by label, foff[C+1] (int64) its segments.  Per face
+ *                          0.5 |(b-a) x (c-a)| and a . (b x c) / 6 in float64 from the fp32 coordinates; each segment is cut into
+ *                          NU_CC_PARTS equal slices, a slice summed by one workgroup in a fixed order into part[C, NU_CC_PARTS, 2]
+ *                          (float64) and pbox[C, NU_CC_PARTS, 6] (fp32 min xyz, max xyz), the slices then in slice order into
+ *                          area[C], volume[C] (float64) and aabb[C, 6]: the same bits on every run
+ *   nu_cc_edge_counts      from the sorted half-edge keys and their permutation: ecount[C, 3] int32 (zeroed here) = unique edges,
+ *                          one-face edges, edges of three or more faces (an edge belongs to the component of its first face)
+ *   nu_cc_corner_keys      keys[nh] int64 = (flabel[f] << 32 | vertex) of every corner; sorted by the caller:
+ *   nu_cc_vertex_counts    vcount[C] int32 (zeroed here) = distinct vertices of each component's faces
+ * The counts use integer atomicAdd (exact in any order); there is no float atomic.
+ * --------------------------------------------------------------------------------------------------------- */
+#define NU_CC_PARTS 32
+int nu_cc_init(int* parent, int n, hipStream_t stream);
+int nu_cc_vertex_links(const int* F, int nf, int* links, hipStream_t stream);
+int nu_cc_edge_links(const long long* skeys, const long long* perm, int nh, int* links, hipStream_t stream);
+int nu_cc_hook(int* parent, int n, const int* links, int nl, hipStream_t stream);
+int nu_cc_compress(int* parent, int n, hipStream_t stream);
+int nu_cc_check(const int* parent, int n, const int* links, int nl, int* flag, hipStream_t stream);
+int nu_cc_mark_used(const int* F, int nf, int nv, int* used, hipStream_t stream);
+int nu_cc_root_flags(const int* parent, const int* used, int n, int* isroot, hipStream_t stream);
+int nu_cc_labels(const int* parent, const int* used, const long long* rinc, int n, int* label, hipStream_t stream);
+int nu_cc_face_labels(const int* F, int nf, const int* vlabel, int* flabel, hipStream_t stream);
+int nu_cc_keep_flags(const int* F, int nf, int nv, const int* flabel, const int* keep_comp, int C, int* fkeep, int* vkeep,
+                     hipStream_t stream);
+int nu_cc_compact(const float* V, int nv, const int* F, int nf, const int* fkeep, const long long* finc, const int* vkeep,
+                  const long long* vinc, float* Vout, int* Fout, hipStream_t stream);
+int nu_cc_face_stats(const float* V, const int* F, int nf, const long long* order, const long long* foff, int C, double* part,
+                     float* pbox, double* area, double* volume, float* aabb, hipStream_t stream);
+int nu_cc_edge_counts(const long long* skeys, const long long* perm, int nh, const int* flabel, int C, int* ecount,
+                      hipStream_t stream);
+int nu_cc_corner_keys(const int* F, int nf, const int* flabel, long long* keys, hipStream_t stream);
+int nu_cc_vertex_counts(const long long* skeys, int nh, int C, int* vcount, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

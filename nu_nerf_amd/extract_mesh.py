@@ -1,10 +1,13 @@
-"""python -m nu_nerf_amd.extract_mesh --cfg CFG [--resolution 1024] [--ckpt PATH] [--out PATH] [--stage2] [--remesh]
+"""python -m nu_nerf_amd.extract_mesh --cfg CFG [--resolution 1024] [--ckpt PATH] [--out PATH] [--stage2] [--remesh] [--fix ...]
 
 extract_mesh_stage1.py on the GPU: the renderer named by the config (`zero_thickness` picks the module set) loads
 data/model/{name}/model.pth (train_glue.save_checkpoint format), its SDF is sampled on the [-1,1]^3 grid (mesh.sdf_grid), marching
 cubes runs at threshold 0, the faces are flipped (np.fliplr: outward normals) and data/meshes/{name}-{step}.ply is written -- the
 raw mesh.  --remesh also writes data/meshes/{name}-{step}_simplified.ply (the file the stage-2 configs' `stage1_mesh_dir` names):
 the reference's pymeshlab isotropic remeshing at 0.5 % of the bounding-box diagonal, here remesh.remesh_isotropic on the GPU.
+--fix also writes data/meshes/{name}-{step}_fixed.ply: the raw mesh without its floaters (components.remove_floaters; the switches
+of python -m nu_nerf_amd.clean_mesh: --keep, --min-area-frac, --min-faces, --drop-cavities, --connectivity), and --remesh then
+remeshes the fixed mesh instead of the raw one.  Without --fix every file is written as before.
 
 --stage2: extract_mesh_stage2.py -- a stage-2 checkpoint; the field is the inner sdf where the stage-1 sdf is < 0 and 1 elsewhere
 (mesh.stage2_inner_grid), no face flip.
@@ -23,6 +26,9 @@ def parse_args(argv=None):
     ap.add_argument('--stage2', action='store_true', help="inner surface of a stage-2 model (extract_mesh_stage2.py)")
     ap.add_argument('--remesh', action='store_true', help="also write the isotropically remeshed OUT_simplified.ply")
     ap.add_argument('--slab-points', type=int, default=None, help="grid points per SDF evaluation slab (default mesh.SLAB_POINTS)")
+    ap.add_argument('--fix', action='store_true', help="also write OUT_fixed.ply without floaters; --remesh then starts from it")
+    from .clean_mesh import add_fix_options
+    add_fix_options(ap)
     return ap.parse_args(argv)
 
 
@@ -64,6 +70,12 @@ def main(argv=None):
     os.makedirs(os.path.dirname(out) or '.', exist_ok=True)
     mesh.write_ply(out, V, F)
     print(f'wrote {out}: {len(V)} vertices, {len(F)} triangles')
+    if flags.fix:
+        from .clean_mesh import fix_kwargs, fixed_path
+        V, F = mesh.remove_floaters(V, F, **fix_kwargs(flags))
+        out_f = fixed_path(out)
+        mesh.write_ply(out_f, V, F)
+        print(f'wrote {out_f}: {len(V)} vertices, {len(F)} triangles')
     if flags.remesh:
         from .remesh import remesh_isotropic, simplified_path
         Vs, Fs = remesh_isotropic(V, F)

@@ -11,6 +11,8 @@ run PyMCubes on a host grid: network/field.py:1286-1317).
   sample_surface    area-weighted deterministic surface samples on the device
   mesh_distance     Chamfer / Hausdorff distances of two meshes from surface samples and LBVH closest points
   remesh_isotropic  isotropic explicit remeshing (split / collapse / flip / relax on the device: remesh.py, csrc/remesh.hip)
+  connected_components / component_stats / remove_floaters   component labelling, statistics and floater removal (components.py,
+                    csrc/components.hip)
 
 Conventions (DESIGN.md "Mesh extraction"): a grid point is INSIDE when u < threshold; triangles wind so that their right-handed
 normal points inside, which is where the reference's raw PyMCubes output of an sdf (positive outside) points before the face flip of
@@ -406,3 +408,22 @@ def remesh_isotropic(V, F, target_len=None, max_surf_dist=None, iterations=3, st
     """Isotropic explicit remeshing on the GPU (the reference's pymeshlab step before stage 2): see remesh.remesh_isotropic."""
     from .remesh import remesh_isotropic as _remesh
     return _remesh(V, F, target_len=target_len, max_surf_dist=max_surf_dist, iterations=iterations, stats=stats)
+
+
+def connected_components(V, F, connectivity='vertex', stats=None):
+    """Component labels of the mesh's faces and vertices on the GPU: see components.connected_components."""
+    from .components import connected_components as _cc
+    return _cc(V, F, connectivity=connectivity, stats=stats)
+
+
+def component_stats(V, F, face_label, C):
+    """Per-component counts, Euler characteristic, AABB, area and signed volume on the GPU: see components.component_stats."""
+    from .components import component_stats as _stats
+    return _stats(V, F, face_label, C)
+
+
+def remove_floaters(V, F, keep=1, min_area_frac=None, min_faces=None, drop_cavities=False, connectivity='vertex', stats=None):
+    """The mesh without its floaters (and, with drop_cavities, its bubbles) on the GPU: see components.remove_floaters."""
+    from .components import remove_floaters as _remove
+    return _remove(V, F, keep=keep, min_area_frac=min_area_frac, min_faces=min_faces, drop_cavities=drop_cavities,
+                   connectivity=connectivity, stats=stats)
