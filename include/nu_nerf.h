@@ -223,6 +223,16 @@ int nu_shade_encode_fwd(const float* nrm, const float* pt, int pt_ld, const floa
 int nu_shade_encode_bwd(const float* nrm, const float* pt, int pt_ld, const float* SD, const float* dOLin, int ld_ol,
                         int sphere, const float* dILin, const float* dNoV, int P, float* dn, float* dMraw, int ldm,
                         hipStream_t stream);
+/* input rows of human_light_predictor (field.py:411-445, :618-629; csrc/human_light.hip): the reflection r of row p meets the XY plane
+ * of the human frame poses[idx[p] / S] ([n_poses,3,4], renderer.get_human_coordinate_poses; S = samples per ray, idx = ray-major sample
+ * index); HLin [P, ld_hl >= 24] = IPE(0.3 inter.xy, rho (0.3 dist)^2, 0, 6) with zero padding, rec [P,4] = hit flag, dist, mean.  Rows
+ * without a hit encode mean = var = 0 (selected, never multiplied).  _bwd ADDS into dn [P,3] (w.r.t. the raw normal) and into column 1
+ * of dMraw, after nu_shade_encode_bwd on the same stream; points and poses carry no gradient. */
+int nu_human_encode_fwd(const float* nrm, const float* pt, int pt_ld, const float* Mraw, int ldm, const int* idx, int S,
+                        const float* poses, int n_poses, int P, int ld_hl, float* HLin, float* rec, hipStream_t stream);
+int nu_human_encode_bwd(const float* nrm, const float* pt, int pt_ld, const float* Mraw, int ldm, const int* idx, int S,
+                        const float* poses, int n_poses, const float* rec, const float* dHLin, int ld_hl, int P, float* dn,
+                        float* dMraw, int lddm, hipStream_t stream);
 /* per-ray mirror query of colour_spec (renderer_zerothick.py:780-781; network/renderer.py:710-725) */
 int nu_spec_encode(const float* dirs, const float* x, int R, int sphere, float* out, int ldo, hipStream_t stream);
 /* NeRF++ inputs (x/|x|, 1/|x|) L=10 and view -d L=4 (renderer_zerothick.py:687-690; field.py:266-269) */
@@ -270,6 +280,17 @@ int nu_shade_combine_bwd(const float* Mraw, int ldm, const float* OLo, const flo
                          const float* RLo, const float* SD, const float* lut, const int* idx, int P, float exp_max,
                          const float* dcolor_rm, float* dMraw, float* dOLo, float* dILo, float* dIWo, float* dRLo,
                          float* dNoV, hipStream_t stream);
+/* the same mix with shader_config.human_light (field.py:630-634, :662-665): HLo [P,4] raw heads of human_light_predictor, hrec [P,4]
+ * the record of nu_human_encode_fwd (column 0 = hit flag).  On hit rows h = exp(min(raw, 0)), w = clamp(exp(min(raw_3, 0)), 0, 1) and
+ * both direct lights become h w + direct (1 - w); a row without a hit is selected through unchanged and its dHLo row is zero.
+ * hw (optional) [P,4]: h w and w (the `human_light` validation image before its sRGB curve). */
+int nu_shade_combine_hl_fwd(const float* Mraw, int ldm, const float* OLo, const float* ILo, const float* IWo,
+                            const float* RLo, const float* HLo, const float* hrec, const float* SD, const float* lut,
+                            const int* idx, int P, float exp_max, float* color_rm, float* aux, float* hw, hipStream_t stream);
+int nu_shade_combine_hl_bwd(const float* Mraw, int ldm, const float* OLo, const float* ILo, const float* IWo,
+                            const float* RLo, const float* HLo, const float* hrec, const float* SD, const float* lut,
+                            const int* idx, int P, float exp_max, const float* dcolor_rm, float* dMraw, float* dOLo,
+                            float* dILo, float* dIWo, float* dRLo, float* dHLo, float* dNoV, hipStream_t stream);
 /* front-to-back composite incl. the background-only composite (:773-779); colour is [R*S,4] = rgb + one auxiliary
  * channel whose composite goes to aux_sum[R] (normal-orientation loss, network/renderer.py:705) */
 int nu_composite_fwd(const float* alpha, const float* color, const unsigned char* inner, int R, int S, float* weights,

@@ -381,6 +381,8 @@ static int skinny_bwd_launch(const float* dy, int ldy, const float* H, int ldh, 
         switch (NO) {
             case 1: if (h16) hipLaunchKernelGGL((skinny_bwd_kernel<1, 256, true>), dim3(blocks), dim3(256), 0, stream, NU_ARGS); else hipLaunchKernelGGL((skinny_bwd_kernel<1, 256, false>), dim3(blocks), dim3(256), 0, stream, NU_ARGS); break;
             case 3: if (h16) hipLaunchKernelGGL((skinny_bwd_kernel<3, 256, true>), dim3(blocks), dim3(256), 0, stream, NU_ARGS); else hipLaunchKernelGGL((skinny_bwd_kernel<3, 256, false>), dim3(blocks), dim3(256), 0, stream, NU_ARGS); break;
+            // the four-wide head of the human-light predictor (h, w; field.py:615): fp32 rows only
+            case 4: if (h16) return NU_ERR_ARG; hipLaunchKernelGGL((skinny_bwd_kernel<4, 256, false>), dim3(blocks), dim3(256), 0, stream, NU_ARGS); break;
             default: return NU_ERR_ARG;
         }
     } else if (K == 1024) {

@@ -400,7 +400,12 @@ static __device__ inline NuLut nu_lut(const float* __restrict__ lut, float u, fl
 // S2 = AppShadingNetwork_S2.forward (field.py:909-1010, the stage-2 surface shading): no refraction light -- the transmitted part
 // continues along the refracted ray -- colour = (diffuse + specular) (1 - T) + F light0 T, second output (1 - F) T (the factor the
 // running transmittance is multiplied with); `internal` (hit from inside the object): the colour is multiplied by zero.
-template <bool BWD, bool S2>
+// HL = shader_config.human_light (field.py:630-634, :662-665; csrc/human_light.hip): HLo [P,4] raw heads of the human-light
+// predictor, hrec [P,4] the encoder's record (column 0: hit flag).  h = exp(min(raw, 0)), w = clamp(exp(min(raw_3, 0)), 0, 1) on
+// hit rows, and both direct lights become h w + direct (1 - w).  A row without a hit keeps its direct lights as they are -- selected,
+// not multiplied -- so it computes what the HL = false kernel computes, and its dHLo row is zero.  hw_out [P,4] (optional, forward):
+// h w and w, the validation image's input.
+template <bool BWD, bool S2, bool HL = false>
 __global__ __launch_bounds__(256) void shade_combine_kernel(
     const float* __restrict__ Mraw, int ldm, const float* __restrict__ OLo, const float* __restrict__ ILo,
     const float* __restrict__ IWo, const float* __restrict__ RLo, const float* __restrict__ SD,
@@ -411,7 +416,10 @@ __global__ __launch_bounds__(256) void shade_combine_kernel(
     const float* __restrict__ dcolor_rm, float* __restrict__ dMraw, float* __restrict__ dOLo, float* __restrict__ dILo,
     float* __restrict__ dIWo, float* __restrict__ dRLo, float* __restrict__ dNoV,
     // S2 only
-    float* __restrict__ rc_out = nullptr, const float* __restrict__ d_rc = nullptr, int internal = 0) {
+    float* __restrict__ rc_out = nullptr, const float* __restrict__ d_rc = nullptr, int internal = 0,
+    // HL only
+    const float* __restrict__ HLo = nullptr, const float* __restrict__ hrec = nullptr, float* __restrict__ dHLo = nullptr,
+    float* __restrict__ hw_out = nullptr) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= P) return;
     const float* mr = Mraw + (long long)p * ldm;
@@ -434,6 +442,25 @@ __global__ __launch_bounds__(256) void shade_combine_kernel(
         ind[c] = expf(fminf(rind[c], exp_max));
         ind0[c] = expf(fminf(rind0[c], exp_max));
         refr[c] = expf(fminf(rrefr[c], exp_max));
+    }
+    // human light: the direct lights of both specular queries are blended before anything else sees them
+    float hl[3], hraw[4], hw = 0.f, dire[3], dire0[3];
+    bool hhit = false;
+    if (HL) {
+        hhit = hrec[(long long)p * 4] > 0.5f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) hraw[c] = HLo[(long long)p * 4 + c];
+        hw = hhit ? fminf(fmaxf(expf(fminf(hraw[3], 0.f)), 0.f), 1.f) : 0.f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            hl[c] = hhit ? expf(fminf(hraw[c], 0.f)) : 0.f;
+            dire[c] = dir[c];
+            dire0[c] = dir0[c];
+            if (hhit) {
+                dir[c] = hl[c] * hw + dire[c] * (1.0f - hw);
+                dir0[c] = hl[c] * hw + dire0[c] * (1.0f - hw);
+            }
+        }
     }
     const float occ = IWo[p] * 0.5f + 0.5f;
     const float oc = fminf(fmaxf(occ, 0.f), 1.f);
@@ -459,6 +486,10 @@ __global__ __launch_bounds__(256) void shade_combine_kernel(
 #pragma unroll
         for (int c = 0; c < 3; ++c) color_rm[k * 4LL + c] = nu_linear_to_srgb(lin[c]);
         if (S2) rc_out[p] = (1.0f - F) * T;
+        if (HL && hw_out) {
+            f32x4 o = {hl[0] * hw, hl[1] * hw, hl[2] * hw, hw};
+            *reinterpret_cast<f32x4*>(hw_out + (long long)p * 4) = o;
+        }
         if (aux) {
             f32x4 a = {occ, T, met, rho};
             *reinterpret_cast<f32x4*>(aux + (long long)p * 4) = a;
@@ -476,6 +507,7 @@ __global__ __launch_bounds__(256) void shade_combine_kernel(
     float* gIL0 = dILo + (long long)p * 4;
     float* gIL1 = dILo + (long long)(P + p) * 4;
     float* gRL = S2 ? nullptr : dRLo + (long long)p * 4;
+    float dhl[3] = {0.f, 0.f, 0.f}, dhw = 0.f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float g = (S2 && internal) ? 0.f : dcolor_rm[k * 4LL + c] * nu_linear_to_srgb_grad(lin[c]);
@@ -508,14 +540,27 @@ __global__ __launch_bounds__(256) void shade_combine_kernel(
         const float dind0 = dlight0 * oc, ddir0 = dlight0 * (1.0f - oc);
         // exp(min(raw, exp_max))
         gOL0[c] = rLd[c] <= exp_max ? dLd * Ld[c] : 0.f;
+        if (HL && hhit) {                // ddir / ddir0 are the cotangents of the blended lights
+            dhl[c] = (ddir + ddir0) * hw;
+            dhw += ddir * (hl[c] - dire[c]) + ddir0 * (hl[c] - dire0[c]);
+            gOL1[c] = rdir[c] <= exp_max ? ddir * (1.0f - hw) * dire[c] : 0.f;
+            gOL2[c] = rdir0[c] <= exp_max ? ddir0 * (1.0f - hw) * dire0[c] : 0.f;
+        } else {
         gOL1[c] = rdir[c] <= exp_max ? ddir * dir[c] : 0.f;
         gOL2[c] = rdir0[c] <= exp_max ? ddir0 * dir0[c] : 0.f;
+        }
         gIL0[c] = rind[c] <= exp_max ? dind * ind[c] : 0.f;
         gIL1[c] = rind0[c] <= exp_max ? dind0 * ind0[c] : 0.f;
         if (!S2) gRL[c] = rrefr[c] <= exp_max ? drefr * refr[c] : 0.f;
     }
     gOL0[3] = 0.f; gOL1[3] = 0.f; gOL2[3] = 0.f; gIL0[3] = 0.f; gIL1[3] = 0.f;
     if (!S2) gRL[3] = 0.f;
+    if (HL) {                            // exp(min(raw, 0)); the clamp of w to [0, 1] passes the gradient on all of exp's range
+        float* gHL = dHLo + (long long)p * 4;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) gHL[c] = (hhit && hraw[c] <= 0.f) ? dhl[c] * hl[c] : 0.f;
+        gHL[3] = (hhit && hraw[3] <= 0.f) ? dhw * hw : 0.f;
+    }
     // occlusion: occ = 0.5 raw + 0.5, clamp passes gradient on [0,1]
     dIWo[p] = (occ >= 0.f && occ <= 1.f) ? docc_c * 0.5f : 0.f;
     // Fresnel: F = clamp(0.04 + 0.96 t^5), t = clamp(1 - NoV)
@@ -557,6 +602,31 @@ extern "C" int nu_shade_combine_bwd(const float* Mraw, int ldm, const float* OLo
     hipLaunchKernelGGL((shade_combine_kernel<true, false>), dim3(nu_cdiv(P, 256)), dim3(256), 0, stream, Mraw, ldm, OLo, ILo, IWo,
                        RLo, SD, lut, idx, P, exp_max, (float*)nullptr, (float*)nullptr, dcolor_rm, dMraw, dOLo, dILo, dIWo,
                        dRLo, dNoV, (float*)nullptr, (const float*)nullptr, 0);
+    return nu_launch_status();
+}
+
+// nu_shade_combine_* with the human-light blend (HLo [P,4] raw heads, hrec [P,4] from nu_human_encode_fwd); hw (optional): [P,4] = h w, w
+extern "C" int nu_shade_combine_hl_fwd(const float* Mraw, int ldm, const float* OLo, const float* ILo, const float* IWo,
+                                       const float* RLo, const float* HLo, const float* hrec, const float* SD, const float* lut,
+                                       const int* idx, int P, float exp_max, float* color_rm, float* aux, float* hw,
+                                       hipStream_t stream) {
+    if (P <= 0) return NU_OK;
+    if (!HLo || !hrec || ((uintptr_t)hw & 15)) return NU_ERR_ARG;
+    hipLaunchKernelGGL((shade_combine_kernel<false, false, true>), dim3(nu_cdiv(P, 256)), dim3(256), 0, stream, Mraw, ldm, OLo, ILo,
+                       IWo, RLo, SD, lut, idx, P, exp_max, color_rm, aux, (const float*)nullptr, (float*)nullptr, (float*)nullptr,
+                       (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (const float*)nullptr, 0,
+                       HLo, hrec, (float*)nullptr, hw);
+    return nu_launch_status();
+}
+extern "C" int nu_shade_combine_hl_bwd(const float* Mraw, int ldm, const float* OLo, const float* ILo, const float* IWo,
+                                       const float* RLo, const float* HLo, const float* hrec, const float* SD, const float* lut,
+                                       const int* idx, int P, float exp_max, const float* dcolor_rm, float* dMraw, float* dOLo,
+                                       float* dILo, float* dIWo, float* dRLo, float* dHLo, float* dNoV, hipStream_t stream) {
+    if (P <= 0) return NU_OK;
+    if (!HLo || !hrec || !dHLo) return NU_ERR_ARG;
+    hipLaunchKernelGGL((shade_combine_kernel<true, false, true>), dim3(nu_cdiv(P, 256)), dim3(256), 0, stream, Mraw, ldm, OLo, ILo,
+                       IWo, RLo, SD, lut, idx, P, exp_max, (float*)nullptr, (float*)nullptr, dcolor_rm, dMraw, dOLo, dILo, dIWo, dRLo,
+                       dNoV, (float*)nullptr, (const float*)nullptr, 0, HLo, hrec, dHLo, (float*)nullptr);
     return nu_launch_status();
 }
 

@@ -78,6 +78,11 @@ class Stage1Engine:
         self.refrac_dim = 3 + 6 * int(cfg.get('refrac_freq', 6))       # field.py:590-591 (real_bottle uses refrac_freq 3)
         self.ld_ol = 160 if self.sphere_direction else 96               # outer_light input 144 / 72 (field.py:594-597)
         self.ld_rl = rup(2 * self.refrac_dim, 32)
+        # shader_config.human_light (field.py:614-634): a fifth predictor stack on 24 IPE columns, padded to the 64-column K the
+        # first layers of the SDF and IoR stacks already run the NT / weight-gradient kernels with
+        # (on only when the owner holds the predictor's parameters: the stage-2 modules carry the key and never build the stack)
+        self.human_light = bool(cfg.get('human_light', False)) and 'color_network.human_light_predictor.0.weight_v' in params
+        self.ld_hl = 64
         # MLP arithmetic: 'fp32' = exact fp32 MFMA (the reference's precision); 'bf16' = operands rounded to bf16 on their
         # way into LDS, bf16 MFMA with fp32 accumulation (BASELINE config 4; no reference counterpart, tolerance in the tests)
         md = str(cfg.get('mlp_dtype', os.environ.get('NU_MLP_DTYPE', 'fp32'))).lower()   # env: run a whole test suite in one mode
@@ -85,6 +90,9 @@ class Stage1Engine:
             raise ValueError(f"mlp_dtype {md!r}: expected 'fp32', 'bf16' or 'bf16x6'")
         # 'bf16x6': fp32-equivalent products on the bf16 pipe (exact 3-way split of both operands, six partial products)
         self.bf16 = 2 if md == 'bf16x6' else (1 if md.startswith('b') else 0)
+        if self.human_light and self.bf16:
+            raise NotImplementedError(f"human_light=True runs the fp32 MLP path only (mlp_dtype {md!r} asked for): its predictor is sequenced "
+                                      "launch by launch and has neither bf16 storage nor pre-split weight planes")
         # 'bf16' stores what only GEMMs touch as bf16 in HBM (weight tables + most hidden activations, include/nu_nerf.h
         # NuOpCtx.h16)
         self.h16 = self.bf16 == 1
@@ -390,6 +398,11 @@ class Stage1Engine:
         self.inner_weight = predictor('color_network.inner_weight', (0, 2, 4, 6), 96)
         self.refrac_light = predictor('color_network.refrac_light', (0, 2, 4, 6), self.ld_rl)
         layers += self.outer_light + self.inner_light + self.inner_weight + self.refrac_light
+        # ---- shading: the human-light predictor (24 -> 256 x 3 -> 4), only when the owner has its parameters ----
+        self.human_pred = None
+        if self.human_light:
+            self.human_pred = predictor('color_network.human_light_predictor', (0, 2, 4, 6), self.ld_hl)
+            layers += self.human_pred
         # ---- stage 2: the IoR / thickness networks (field.py:1046-1087: 39 -> 256 ReLU -> 256 ReLU -> 256 -> 1), when the owner
         # has them ----
         self.small = {}
@@ -948,10 +961,12 @@ class Stage1Engine:
                     self.nt(addr(dA), 256, addr(*lay.WpT), lay.ldT, rows, dx_cols, 256, addr(dX), lddx, EPI_PLAIN)
 
     # ------------------------------------------------------------------ shading stack
-    def shading_forward(self, a, pt, idx, P, color_rm, extra_dirs=None, extra_pts=None):
+    def shading_forward(self, a, pt, idx, P, color_rm, extra_dirs=None, extra_pts=None, human_poses=None, S_ray=0):
         """Materials -> encodings -> 4 light predictors -> combine (field.py:684-777).
         a: SDF activations (YX, E, n).  extra_dirs [R,3]: per-ray directions whose mirror query IDE(d,0)
-        rides along the outer_light batch (colour_spec, renderer_zerothick.py:780-781)."""
+        rides along the outer_light batch (colour_spec, renderer_zerothick.py:780-781).
+        human_light: human_poses [n,3,4] holds one human frame per ray, row p takes human_poses[idx[p] // S_ray]; the fifth
+        predictor and the blend run launch by launch (nu_shading_stack_* does not know them)."""
         if self.light_pos_freq != 6:
             raise NotImplementedError("the fused stage-1 shading encodes positions with 6 frequencies (every stage-1 config); "
                                       "light_pos_freq != 6 runs through the network-level ops (nets.py / shading_glue.py)")
@@ -959,7 +974,13 @@ class Stage1Engine:
         e = self.empty
         s = {'P': P}
         YX = a['YX']
-        if self._use_c():
+        if self.human_light:
+            if human_poses is None or S_ray <= 0:
+                raise ValueError("human_light=True needs the rays' human poses (renderer._process_ray_batch) and the samples per ray")
+            human_poses = human_poses.to(torch.float32).contiguous()
+            if human_poses.dim() != 3 or tuple(human_poses.shape[1:]) != (3, 4):
+                raise ValueError(f"human_poses must be [n,3,4], got {tuple(human_poses.shape)}")
+        if self._use_c() and not self.human_light:
             return self._c_shading_forward(a, pt, idx, P, color_rm, extra_dirs, extra_pts)
         # materials: layer 0 batched (N=1024), layers 1-2 grouped x4, block-diagonal 6-wide head
         M1, M2, M3 = e(P, 1024), e(P, 1024), e(P, 1024)
@@ -995,6 +1016,17 @@ class Stage1Engine:
             self.skinny_fwd(addr(Hs[2]), 256, rows, 256, addr(*lay.Wp), 256, addr(lay.b), no, addr(out), ldo)
         s.update(OLo=OLo, ILo=ILo, IWo=IWo, RLo=RLo)
         s['aux'] = e(P, 4)
+        if self.human_light:
+            ld_hl, head = self.ld_hl, self.human_pred[3]
+            HLin, hrec, HLo, hw = e(P, ld_hl), e(P, 4), e(P, 4), e(P, 4)
+            lib.nu_human_encode_fwd(addr(a['n']), addr(pt), 8, addr(Mraw), 8, addr(idx), S_ray, addr(human_poses),
+                                    human_poses.shape[0], P, ld_hl, addr(HLin), addr(hrec), S)
+            s['HLh'] = self.relu_stack_fwd(self.human_pred, HLin, ld_hl, P)
+            self.skinny_fwd(addr(s['HLh'][2]), 256, P, 256, addr(*head.Wp), 256, addr(head.b), 4, addr(HLo), 4)
+            s.update(HLin=HLin, hrec=hrec, HLo=HLo, hw=hw, human_poses=human_poses, S_ray=S_ray)
+            lib.nu_shade_combine_hl_fwd(addr(Mraw), 8, addr(OLo), addr(ILo), addr(IWo), addr(RLo), addr(HLo), addr(hrec), addr(SD),
+                                        addr(self.lut), addr(idx), P, self.exp_max, addr(color_rm), addr(s['aux']), addr(hw), S)
+            return s
         lib.nu_shade_combine_fwd(addr(Mraw), 8, addr(OLo), addr(ILo), addr(IWo), addr(RLo), addr(SD),
                                  addr(self.lut), addr(idx), P, self.exp_max, addr(color_rm), addr(s['aux']), S)
         return s
@@ -1073,9 +1105,17 @@ class Stage1Engine:
         if self._use_c() and 'cb' in s:
             return self._c_shading_backward(a, s, pt, idx, dcolor_rm, flat, d_spec_raw, d_occ_raw, d_mat_raw)
         dMraw, dOLo, dILo, dIWo, dRLo, dNoV = e(P, 8), e(rows_ol, 4), e(2 * P, 4), e(P), e(P, 4), e(P)
-        lib.nu_shade_combine_bwd(addr(s['Mraw']), 8, addr(s['OLo']), addr(s['ILo']), addr(s['IWo']), addr(s['RLo']),
-                                 addr(s['SD']), addr(self.lut), addr(idx), P, self.exp_max, addr(dcolor_rm),
-                                 addr(dMraw), addr(dOLo), addr(dILo), addr(dIWo), addr(dRLo), addr(dNoV), S)
+        hl = 'HLo' in s
+        if hl:
+            dHLo, dHLin = e(P, 4), e(P, self.ld_hl)
+            lib.nu_shade_combine_hl_bwd(addr(s['Mraw']), 8, addr(s['OLo']), addr(s['ILo']), addr(s['IWo']), addr(s['RLo']),
+                                        addr(s['HLo']), addr(s['hrec']), addr(s['SD']), addr(self.lut), addr(idx), P, self.exp_max,
+                                        addr(dcolor_rm), addr(dMraw), addr(dOLo), addr(dILo), addr(dIWo), addr(dRLo), addr(dHLo),
+                                        addr(dNoV), S)
+        else:
+            lib.nu_shade_combine_bwd(addr(s['Mraw']), 8, addr(s['OLo']), addr(s['ILo']), addr(s['IWo']), addr(s['RLo']),
+                                     addr(s['SD']), addr(self.lut), addr(idx), P, self.exp_max, addr(dcolor_rm),
+                                     addr(dMraw), addr(dOLo), addr(dILo), addr(dIWo), addr(dRLo), addr(dNoV), S)
         if R:
             if d_spec_raw is not None:
                 dOLo[3 * P:, :3] = d_spec_raw
@@ -1086,15 +1126,25 @@ class Stage1Engine:
             dIWo += d_occ_raw
         if d_mat_raw is not None:
             dMraw += d_mat_raw
+        if hl:
+            # the fifth stack's three weight gradients form a queue of their own.  Queued with the pass's, they push its 256 x 256-tile
+            # class over a batch table: one more launch of a grid that is sized for the whole class, i.e. every launch of the class
+            # a third longer (measured at 4096 rays: +13.0 ms per step in gemm_tn2b_kernel, the key +18.6 ms per step instead of +5.5)
+            with self.wgrad_batch() as wb:
+                head = self.human_pred[3]
+                dH3 = wb.keep(e(P, 256))
+                self.skinny_bwd(addr(dHLo), 4, addr(s['HLh'][2]), 256, P, 256, addr(*head.Wp), 256, 4, addr(dH3), 256, 1, 0,
+                                addr(*head.dWp), head.ldd, addr(flat, head.db_off))
+                self.relu_stack_bwd(self.human_pred, s['HLin'], self.ld_hl, P, s['HLh'], dH3, flat, dHLin, self.ld_hl, self.ld_hl)
         with self.wgrad_batch() as wb:        # the pass's weight gradients: one queue, launched together at the end of the block
             # heads + hidden stacks of the four light predictors
             ld_ol, ld_rl = self.ld_ol, self.ld_rl
             dOLin, dILin = e(rows_ol, ld_ol), e(2 * P, 128)
-            for layers, Hs, dy, ldy, rows, no, X, ldx, dX, lddx, dxc in (
-                    (self.outer_light, s['OLh'], dOLo, 4, rows_ol, 3, s['OLin'], ld_ol, dOLin, ld_ol, ld_ol),
-                    (self.inner_light, s['ILh'], dILo, 4, 2 * P, 3, s['ILin'], 128, dILin, 128, 128),
-                    (self.inner_weight, s['IWh'], dIWo, 1, P, 1, s['IWin'], 96, None, 0, 0),
-                    (self.refrac_light, s['RLh'], dRLo, 4, P, 3, s['RLin'], ld_rl, None, 0, 0)):
+            stacks = [(self.outer_light, s['OLh'], dOLo, 4, rows_ol, 3, s['OLin'], ld_ol, dOLin, ld_ol, ld_ol),
+                      (self.inner_light, s['ILh'], dILo, 4, 2 * P, 3, s['ILin'], 128, dILin, 128, 128),
+                      (self.inner_weight, s['IWh'], dIWo, 1, P, 1, s['IWin'], 96, None, 0, 0),
+                      (self.refrac_light, s['RLh'], dRLo, 4, P, 3, s['RLin'], ld_rl, None, 0, 0)]
+            for layers, Hs, dy, ldy, rows, no, X, ldx, dX, lddx, dxc in stacks:
                 head = layers[3]
                 dH3 = wb.keep(e(rows, 256))
                 self.skinny_bwd(addr(dy), ldy, addr(Hs[2]), 256, rows, 256, addr(*head.Wp), 256, no, addr(dH3), 256, 1, 0,
@@ -1103,6 +1153,10 @@ class Stage1Engine:
             dn = e(P, 3)
             lib.nu_shade_encode_bwd(addr(a['n']), addr(pt), 8, addr(s['SD']), addr(dOLin), ld_ol,
                                     1 if self.sphere_direction else 0, addr(dILin), addr(dNoV), P, addr(dn), addr(dMraw), 8, S)
+            if hl:          # adds into dn and the roughness column of dMraw
+                hp = s['human_poses']
+                lib.nu_human_encode_bwd(addr(a['n']), addr(pt), 8, addr(s['Mraw']), 8, addr(idx), s['S_ray'], addr(hp), hp.shape[0],
+                                        addr(s['hrec']), addr(dHLin), self.ld_hl, P, addr(dn), addr(dMraw), 8, S)
             # materials backward
             db0, db12, db6 = self.mat_db
             dM3 = wb.keep(e(P, 1024))
@@ -1299,7 +1353,7 @@ class Stage1Engine:
         return out
 
     # ------------------------------------------------------------------ render_core
-    def _render_forward_inner(self, ctx, out, o, d, P_in, pt_in, idx_in, alpha_rm, color_rm, anneal, spec_pts):
+    def _render_forward_inner(self, ctx, out, o, d, P_in, pt_in, idx_in, alpha_rm, color_rm, anneal, spec_pts, human_poses=None):
         """The inner-point chain of render_forward (SDF, normal, NeuS alpha, shading) on the caller's stream."""
         lib, S_, e = self.lib, self.stream(), self.empty
         # unit ray directions for the per-ray mirror query (dirs[:,0,:] in the reference)
@@ -1318,7 +1372,8 @@ class Stage1Engine:
             var = self.p['deviation_network.variance']
             lib.nu_neus_alpha_fwd(addr(a['YX']), 288, addr(a['n']), addr(pt_in), addr(idx_in), P_in,
                                   addr(var), anneal, addr(alpha_rm), addr(gerr), addr(color_rm), S_)
-            s = self.shading_forward(a, pt_in, idx_in, P_in, color_rm, extra_dirs=du, extra_pts=spec_pts)
+            s = self.shading_forward(a, pt_in, idx_in, P_in, color_rm, extra_dirs=du, extra_pts=spec_pts,
+                                     human_poses=human_poses, S_ray=ctx['S'])
             ctx.update(sdf=a, shade=s)
             out['gradient_error'] = gerr
             out['spec_raw'] = s['OLo'][3 * P_in:, :3]
@@ -1327,13 +1382,16 @@ class Stage1Engine:
             out['aux'] = s['aux']
             out['normal_raw'] = a['n']
 
-    def render_forward(self, o, d, z, anneal, want_weights=False, spec_pts=None):
+    def render_forward(self, o, d, z, anneal, want_weights=False, spec_pts=None, human_poses=None):
         """Stage-1 render_core forward (renderer_zerothick.py:725-820) on R rays with S samples each.
+        human_poses [R,3,4]: the rays' human frames, read only with human_light (field.py:618-634).
         Returns (outputs dict of tensors, ctx) ; one host sync (the inner-point count)."""
         lib, S_ = self.lib, self.stream()
         e = self.empty
         R, S = z.shape
         o, d, z = o.contiguous(), d.contiguous(), z.contiguous()
+        if self.human_light and (human_poses is None or human_poses.shape[0] != R):
+            raise ValueError("human_light=True: render needs human_poses [R,3,4], one human frame per ray (_process_ray_batch)")
         cnt, off, tot = e(R, dtype=torch.int32), e(R, dtype=torch.int32), e(2, dtype=torch.int32)
         lib.nu_partition_count(addr(o), addr(d), addr(z), R, S, addr(cnt), addr(off), addr(tot), S_)
         P_in = int(tot[0].item())
@@ -1360,7 +1418,8 @@ class Stage1Engine:
                     ctx['nerf'] = self.nerf_forward(pt_out, idx_out, P_out, alpha_rm, color_rm)
             elif P_out > 0:
                 ctx['nerf'] = self.nerf_forward(pt_out, idx_out, P_out, alpha_rm, color_rm)
-            self._render_forward_inner(ctx, out, o, d, P_in, pt_in, idx_in, alpha_rm, color_rm, anneal, spec_pts)
+            self._render_forward_inner(ctx, out, o, d, P_in, pt_in, idx_in, alpha_rm, color_rm, anneal, spec_pts,
+                                       human_poses if self.human_light else None)
         finally:
             if two:
                 fk.__exit__(None, None, None)
@@ -1412,7 +1471,7 @@ class Stage1Engine:
             self.zero_stale_wgrads(self.nerf + [self.nerf_feat, self.nerf_alpha, self.nerf_view, self.nerf_rgb])
         if P_in == 0:
             self.zero_stale_wgrads(self.sdf + self.mat_layers + self.outer_light + self.inner_light +
-                                   self.inner_weight + self.refrac_light)
+                                   self.inner_weight + self.refrac_light + (self.human_pred or []))
         if P_in > 0:
             a, s = ctx['sdf'], ctx['shade']
             d_mat = None

@@ -254,7 +254,7 @@ class _FusedLossFn(torch.autograd.Function):
 _FUSED_TYPES = None
 
 
-def fused_stage1_loss(renderer, batch, step, losses, rand=None, reducer=None):
+def fused_stage1_loss(renderer, batch, step, losses, rand=None, reducer=None, poses=None):
     """One training forward + the trainer's total (train/trainer_zero.py:153-161) with the loss assembly on the HIP loss
     kernels: NeRFRenderLoss (charbonier), EikonalLoss, OuterRegLoss and NormalOrientationLoss are fused; StdRecorder, OccLoss,
     InitSDFRegLoss and MaskLoss entries keep their (O(1)-sized) torch form and are added on.  Returns (total, log, outputs)
@@ -265,19 +265,21 @@ def fused_stage1_loss(renderer, batch, step, losses, rand=None, reducer=None):
     the union of all ranks' subsets (`parallel.dp_weight_outputs`; the eikonal weight goes to the loss kernels as a device scalar),
     so the data-parallel step runs the SAME fused assembly as the single-GPU step and its all-reduced gradient equals the
     single-process one up to the two approximations stated at dp_weight_outputs (the 2048-point occlusion cap, the init-SDF
-    normalisers of the first 1000 steps)."""
+    normalisers of the first 1000 steps).
+
+    poses: the camera poses of a real-capture batch {'dirs', 'idxs', 'rgbs'} (train_step_rays)."""
     from .parallel import dp_weight_outputs
     pw = None
     dp = reducer is not None and not getattr(reducer, 'solo', reducer.world <= 1)
     real_cand = getattr(renderer, 'candidate_rays', False)
     if renderer.cfg['rgb_loss'] != 'charbonier' or not any(isinstance(ls, NeRFRenderLoss) for ls in losses) or (dp and real_cand):
         # (the candidate-ray regulariser of the real-capture renderer takes its weight on the eager outputs)
-        out = renderer.train_step_rays(batch, step, rand=rand)
+        out = renderer.train_step_rays(batch, step, rand=rand, poses=poses)
         if dp:
             dp_weight_outputs(out, reducer, renderer)
         total, log = total_loss(out, losses, step)
         return total, log, out
-    out = renderer.train_step_rays(batch, step, rand=rand, fused=True)
+    out = renderer.train_step_rays(batch, step, rand=rand, fused=True, poses=poses)
     if dp:
         pw = dp_weight_outputs(out, reducer, renderer, fused_eikonal=True)['inner']
     raw = out.pop('_raw')

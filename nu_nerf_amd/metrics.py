@@ -114,7 +114,8 @@ def panel(data_pr, stage2=False):
     """uint8 [H, W, 3] on the device: the picture the reference's metric classes save.  Row 1 is gt_rgb | ray_rgb | normal; below
     it the maps of draw_materials (those of the 12 keys that data_pr has, four per row) or, for stage 2, of draw_materials_s2
     (three, one row); one-channel maps are repeated to three.  Rows narrower than the widest are padded with zeros on the right
-    (concat_images_list, utils/draw_utils.py:172-192).  The text labels cv2.putText draws on the material maps are not reproduced."""
+    (concat_images_list, utils/draw_utils.py:172-192).  The text labels cv2.putText draws on the material maps are not reproduced.
+    With shader_config.human_light the outputs carry `human_light`: it is appended to row 1 (network/metrics.py:118-119)."""
     pr = to_uint8(data_pr['ray_rgb'])
     h, w = int(pr.shape[0]), int(pr.shape[1])
 
@@ -123,7 +124,8 @@ def panel(data_pr, stage2=False):
         return img.expand(h, w, 3) if img.shape[-1] == 1 else img
 
     keys = [k for k in (_STAGE2_KEYS if stage2 else _SHAPE_KEYS) if k in data_pr]
-    rows = [['gt_rgb', 'ray_rgb', 'normal']] + [keys[i:i + 4] for i in range(0, len(keys), 4)]
+    rows = [['gt_rgb', 'ray_rgb', 'normal'] + (['human_light'] if 'human_light' in data_pr else [])]
+    rows += [keys[i:i + 4] for i in range(0, len(keys), 4)]
     out = torch.zeros(h * len(rows), w * max(len(r) for r in rows), 3, dtype=torch.uint8, device=pr.device)
     for ri, row in enumerate(rows):
         for ci, k in enumerate(row):

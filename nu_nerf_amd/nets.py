@@ -449,6 +449,9 @@ class Stage1Nets:
                            ('inner_weight', eng.inner_weight), ('refrac_light', eng.refrac_light)):
             names, params = sel(lambda n, nm=nm: n.startswith('color_network.' + nm + '.'))
             self.stack[nm] = (layers, names, params)
+        if getattr(eng, 'human_pred', None):          # shader_config.human_light: the fifth stack, last of the shading layers
+            names, params = sel(lambda n: n.startswith('color_network.human_light_predictor.'))
+            self.stack['human_light_predictor'] = (eng.human_pred, names, params)
         self.ior_names, _ = sel(lambda n: n.startswith('ior_network.'))
         self.thick_names, _ = sel(lambda n: n.startswith('thickness_network.'))
         self.all_names = [n for n in g if n in named and isinstance(named[n], torch.nn.Parameter)]

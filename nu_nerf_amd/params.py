@@ -60,9 +60,15 @@ def predictor_dims(sphere_direction=False, refrac_freq=6, light_pos_freq=6):
     ]
 
 
-def init_stage1_params(seed=6033, sphere_direction=False, sdf_bias=0.5, inv_s_init=0.3, refrac_freq=6, light_pos_freq=6):
+HUMAN_LIGHT_DIMS = ((24, 256), (256, 256), (256, 256), (256, 4))      # make_predictor(2 * 2 * 6, 4, activation='exp'), field.py:615
+
+
+def init_stage1_params(seed=6033, sphere_direction=False, sdf_bias=0.5, inv_s_init=0.3, refrac_freq=6, light_pos_freq=6,
+                       human_light=False):
     """OrderedDict name -> np.float32 array, in the reference module-construction order
-    (renderer_zerothick.py:144-162)."""
+    (renderer_zerothick.py:144-162).  human_light=True adds the twelve color_network.human_light_predictor.* tensors after
+    refrac_light (field.py:613-616, head bias log 0.01); their draws come from a generator of their own, so every other tensor
+    is the same with the key on and off."""
     rng = np.random.Generator(np.random.PCG64(seed))
     p = OrderedDict()
 
@@ -114,6 +120,13 @@ def init_stage1_params(seed=6033, sphere_direction=False, sdf_bias=0.5, inv_s_in
             if j == 3 and last_bias is not None:
                 b = np.full((no,), last_bias, np.float32)
             _put_wn(p, f"color_network.{name}.{2 * j}", w, b)
+    if human_light:
+        hrng = np.random.Generator(np.random.PCG64([seed, 0x68756d616e]))
+        for j, (ki, no) in enumerate(HUMAN_LIGHT_DIMS):
+            w, b = _linear_default(hrng, no, ki)
+            if j == 3:
+                b = np.full((no,), math.log(0.01), np.float32)
+            _put_wn(p, f"color_network.human_light_predictor.{2 * j}", w, b)
 
     # ---- InfOutNetwork (field.py:1020-1036): constructed, never evaluated ----
     chain = [(63, 256), (256, 256), (256, 256), (256, 256), (256, 3)]

@@ -146,10 +146,10 @@ class AppShadingNetwork(nn.Module):
     def __init__(self, cfg):
         super().__init__()
         self.cfg = {**self.default_cfg, **cfg}
-        if self.cfg['human_light']:
-            raise NotImplementedError("human_light=True is outside the stage-1 hot path of the supported configs")
         for name, k, n_out, _ in predictor_dims(self.cfg['sphere_direction'], self.cfg['refrac_freq'], self.cfg['light_pos_freq']):
             setattr(self, name, _predictor(k, n_out))
+        if self.cfg['human_light']:       # the photographer's reflection (field.py:613-616): IPE(24) -> 4, registered after refrac_light
+            self.human_light_predictor = _predictor(24, 4)
         self.register_buffer('FG_LUT', torch.zeros(1, 256, 256, 2))
 
 
@@ -169,8 +169,8 @@ class _RenderCoreFn(torch.autograd.Function):
     """render_core as ONE differentiable op: forward + hand-derived backward, both sequences of HIP kernels."""
 
     @staticmethod
-    def forward(ctx, engine, o, d, z, anneal, train_inv_s, names, spec_pts, *params):
-        out, c = engine.render_forward(o, d, z, anneal, spec_pts=spec_pts)
+    def forward(ctx, engine, o, d, z, anneal, train_inv_s, names, spec_pts, human_poses, *params):
+        out, c = engine.render_forward(o, d, z, anneal, spec_pts=spec_pts, human_poses=human_poses)
         ctx.engine, ctx.c, ctx.names, ctx.train_inv_s = engine, c, names, train_inv_s
         ctx.set_materialize_grads(False)
         dev = o.device
@@ -203,7 +203,7 @@ class _RenderCoreFn(torch.autograd.Function):
                 continue
             grads.append(flat[off:off + eng.grad_numel[n]].view(shape))
         ctx.c = None
-        return (None,) * 8 + tuple(grads)
+        return (None,) * 9 + tuple(grads)
 
 
 class _SdfValueFn(torch.autograd.Function):
@@ -274,6 +274,13 @@ class NeROShapeRenderer(nn.Module):
         self.deviation_network = SingleVarianceNetwork(c['inv_s_init'])
         self.outer_nerf = NeRFNetwork()
         self.color_network = AppShadingNetwork(c['shader_config'])
+        if self.color_network.cfg['human_light']:
+            if self.is_nerf:
+                raise ValueError("shader_config.human_light=True needs the camera poses of a real capture (is_nerf: false): the "
+                                 "NeRF-synthetic ray batches carry rays_o / rays_d only, there is no human frame to intersect")
+            md = str(c.get('mlp_dtype', 'fp32')).lower()
+            if md not in ('fp32', 'f32', 'float32'):
+                raise NotImplementedError(f"shader_config.human_light=True runs the fp32 MLP path only (mlp_dtype {md!r} asked for)")
         self.infinity_far_bkgr = InfOutNetwork()
         self._engine = None
         self._init_parameters()
@@ -287,7 +294,8 @@ class NeROShapeRenderer(nn.Module):
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
         init = init_stage1_params(seed, sphere_direction=self.color_network.cfg['sphere_direction'],
                                   sdf_bias=self.cfg['sdf_bias'], inv_s_init=self.cfg['inv_s_init'],
-                                  refrac_freq=self.color_network.cfg['refrac_freq'])
+                                  refrac_freq=self.color_network.cfg['refrac_freq'],
+                                  human_light=bool(self.color_network.cfg['human_light']))
         self.load_param_dict(init)
 
     def load_param_dict(self, arrays):
@@ -426,7 +434,7 @@ class NeROShapeRenderer(nn.Module):
         return torch.clamp(mid - 1.0, min=1e-3), mid + 1.0
 
     def get_human_coordinate_poses(self, poses):
-        """renderer_zerothick.py:329-345 / renderer.py:329-345 (only consumed by human_light, which is off in every config)."""
+        """renderer_zerothick.py:329-345 / renderer.py:329-345 (consumed by shader_config.human_light only)."""
         pn = poses.shape[0]
         cam_cen = (-poses[:, :, :3].permute(0, 2, 1) @ poses[:, :, 3:])[..., 0]
         if not self.cfg.get('fixed_camera', False):
@@ -508,7 +516,8 @@ class NeROShapeRenderer(nn.Module):
         eng.occ_sdf_thresh = float(cfg['occ_sdf_thresh']) if early else None
         try:
             rgb, acc, rgb_bg, gerr, spec_raw, occ_raw, sdf_in, nrm_sum, trans, metal = _RenderCoreFn.apply(
-                eng, rays_o, rays_d, z_vals, float(cos_anneal_ratio), not frozen, self._grad_names, spec_pts, *self._grad_params)
+                eng, rays_o, rays_d, z_vals, float(cos_anneal_ratio), not frozen, self._grad_names, spec_pts,
+                human_poses if eng.human_light else None, *self._grad_params)
         finally:
             eng.occ_sdf_thresh = None
         exp_max = eng.exp_max
@@ -551,7 +560,7 @@ class NeROShapeRenderer(nn.Module):
                 outputs['loss_occ'] = torch.zeros(1, device=rgb.device)
         if not is_train:
             from .validation import composite_weights, compute_validation_info
-            outputs.update(compute_validation_info(self, z_vals, rays_o, rays_d, composite_weights(eng, c), step))
+            outputs.update(compute_validation_info(self, z_vals, rays_o, rays_d, composite_weights(eng, c), step, human_poses))
         return outputs
 
     def _spec_query_points(self, rays_o, rays_d, z_vals):
@@ -630,9 +639,11 @@ class NeROShapeRenderer(nn.Module):
             batch, poses, rn, h, w = self._construct_nerf_ray_batch(info, dev, is_train=False)
         else:
             batch, poses, rn, h, w = self._construct_ray_batch(info, dev)
-            ro, rd, _, _, _ = self._process_ray_batch(batch, poses.float().to(dev))
+            ro, rd, _, _, hp = self._process_ray_batch(batch, poses.float().to(dev))
             batch = {'rays_o': ro, 'rays_d': rd, 'rgbs': batch['rgbs']}
-        batch = {k: v for k, v in batch.items() if k in ('rays_o', 'rays_d', 'rgbs')}
+            if self.color_network.cfg['human_light']:
+                batch['human_poses'] = hp
+        batch = {k: v for k, v in batch.items() if k in ('rays_o', 'rays_d', 'rgbs', 'human_poses')}
         depth = info['depths'][0].reshape(h, w, 1).float().cpu() if 'depths' in info else torch.zeros(h, w, 1)
         mask = (info['masks'][0].reshape(h, w, 1) > 0).to(torch.int32).cpu() if 'masks' in info else torch.zeros(h, w, 1, dtype=torch.int32)
         return batch, h, w, depth, mask

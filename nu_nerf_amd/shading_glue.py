@@ -34,8 +34,20 @@ def sphere_point(points, dirs):
     return F.normalize(sp + dirs * get_sphere_intersection(sp, dirs), dim=-1)
 
 
-def lights(nets, exp_max, points, n, refl, rough, sphere=False, detail=False, pos_freq=6):
-    """The three outer_light and two inner_light queries + the occlusion weight (field.py:636-682), row-batched."""
+def human_light(nets, points, normals, view_dirs, m_raw, human_poses):
+    """predict_human_light (field.py:618-634) on the network ops: (h [P,3], w [P,1]), both exactly zero on rows whose reflection
+    misses the photographer's disc (selected by the encoder's hit flag, not multiplied)."""
+    from . import stage2_ops as O
+    HL, rec = O.human_encode(nets.eng, points, normals, view_dirs, m_raw, human_poses)
+    raw = nets.predictor('human_light_predictor', HL)
+    hit = rec[:, 0:1] > 0.5
+    out = torch.where(hit, torch.exp(torch.clamp(raw, max=0.0)), torch.zeros_like(raw))
+    return out[:, :3], torch.clamp(out[:, 3:], 0.0, 1.0)
+
+
+def lights(nets, exp_max, points, n, refl, rough, sphere=False, detail=False, pos_freq=6, human=None):
+    """The three outer_light and two inner_light queries + the occlusion weight (field.py:636-682), row-batched.
+    human = (h, w): both direct specular lights become h w + direct (1 - w) (field.py:662-665)."""
     P = points.shape[0]
     one, zero = torch.ones_like(rough), torch.zeros_like(rough)
     enc = torch.cat([G.ide(n, one), G.ide(refl, rough), G.ide(refl, zero)], 0)
@@ -51,27 +63,43 @@ def lights(nets, exp_max, points, n, refl, rough, sphere=False, detail=False, po
                                                                           torch.cat([pe, enc[2 * P:]], -1)], 0)), max=exp_max))
     occ = nets.predictor('inner_weight', torch.cat([pe.detach(), G.embed(refl, 6).detach()], -1)) * 0.5 + 0.5
     occ_c = torch.clamp(occ, 0.0, 1.0)
-    light = li[:P] * occ_c + lo[P:2 * P] * (1 - occ_c)
-    light0 = li[P:] * occ_c + lo[2 * P:] * (1 - occ_c)
+    d1, d0 = lo[P:2 * P], lo[2 * P:]
+    if human is not None:
+        h, w = human
+        d1, d0 = h * w + d1 * (1 - w), h * w + d0 * (1 - w)
+    light = li[:P] * occ_c + d1 * (1 - occ_c)
+    light0 = li[P:] * occ_c + d0 * (1 - occ_c)
     if detail:
         return lo[:P], light, light0, occ, li[:P] * occ_c
     return lo[:P], light, light0
 
 
-def shade(nets, scfg, lut, points, normals, view_dirs, feats, s2=False, is_internal=False, inter_results=False, aux=None):
+def _wants_human(scfg, s2, human_poses):
+    if s2 or not scfg.get('human_light', False):
+        return False
+    if human_poses is None:
+        raise ValueError("shader_config.human_light=True: shade needs human_poses [P,3,4], one human frame per point")
+    return True
+
+
+def shade(nets, scfg, lut, points, normals, view_dirs, feats, s2=False, is_internal=False, inter_results=False, aux=None,
+          human_poses=None):
     """AppShadingNetwork.forward (field.py:684-777) or, with s2=True, AppShadingNetwork_S2.forward (field.py:909-1010): materials ->
     ONE kernel for every stack's padded input rows (n^, v^, NoV, r, IDE / position / refraction codes, sphere points; gradients to
     points, normals, view directions and the roughness logit) -> the four stacks -> the BRDF mix as one kernel pair on the raw
-    heads.  inter_results=True (validation images of test_step) returns the intermediate terms as well."""
+    heads.  inter_results=True (validation images of test_step) returns the intermediate terms as well.
+    human_poses [P,3,4] (stage-1 form with shader_config.human_light): the fifth stack and the blended combine (nu_human_encode_*,
+    nu_shade_combine_hl_*); the images then carry `human_light`."""
     if not points.is_cuda:
         from ._lib import NuNerfLibraryError
         raise NuNerfLibraryError("shade needs CUDA(HIP) tensors: there is no CPU fallback for the product path")
     if inter_results:
-        return _shade_with_images(nets, scfg, lut, points, normals, view_dirs, feats, s2, is_internal)
+        return _shade_with_images(nets, scfg, lut, points, normals, view_dirs, feats, s2, is_internal, human_poses)
     exp_max = scfg['light_exp_max']
     rl_max = scfg.get('refrac_exp_max', exp_max)
     pos_freq = int(scfg.get('light_pos_freq', 6))
     sphere = bool(scfg.get('sphere_direction', False))
+    human = _wants_human(scfg, s2, human_poses)
     if points.shape[0] == 0:
         if aux is not None:
             aux.update(occ_raw=points.new_zeros(0, 1), reflective=points.new_zeros(0, 3))
@@ -90,11 +118,16 @@ def shade(nets, scfg, lut, points, normals, view_dirs, feats, s2=False, is_inter
             rl = torch.clamp(rl, max=rl_max)     # the kernel's own min(., exp_max) is then the identity
     if aux is not None:          # what the occlusion probe of the caller needs (occ_info of field.py:1533-1537)
         aux.update(occ_raw=iw, reflective=SD[:, 8:11])
+    if human and points.shape[0] > 0:
+        HL, rec = O.human_encode(nets.eng, points, normals, view_dirs, m_raw, human_poses)
+        hl = nets.predictor('human_light_predictor', HL)
+        color, _ = O.shade_combine_hl(nets.eng, m_raw, ol, il, iw, rl, hl, rec, nov1[:, None], lut, exp_max)
+        return color, None
     color, rc = O.shade_combine(nets.eng, m_raw, ol, il, iw, rl, nov1[:, None], lut, exp_max, s2=s2, internal=is_internal)
     return color, (rc if s2 else None)
 
 
-def _shade_with_images(nets, scfg, lut, points, normals, view_dirs, feats, s2, is_internal):
+def _shade_with_images(nets, scfg, lut, points, normals, view_dirs, feats, s2, is_internal, human_poses=None):
     """The validation images (field.py:747-770, :984-1003): the shading formulas term by term on the outputs of the network ops."""
     exp_max = scfg['light_exp_max']
     rl_max = scfg.get('refrac_exp_max', exp_max)
@@ -103,9 +136,14 @@ def _shade_with_images(nets, scfg, lut, points, normals, view_dirs, feats, s2, i
     n, v = F.normalize(normals, dim=-1), F.normalize(view_dirs, dim=-1)
     nov = torch.sum(n * v, -1, keepdim=True)
     refl = nov * n * 2 - v
-    m = torch.sigmoid(nets.materials(feats, points))
+    m_raw = nets.materials(feats, points)
+    m = torch.sigmoid(m_raw)
     metallic, rough, albedo, trans = m[:, 0:1], m[:, 1:2], m[:, 2:5], m[:, 5:6]
-    diffuse_light, light, light0, occ, indirect = lights(nets, exp_max, points, n, refl, rough, sphere, detail=True, pos_freq=pos_freq)
+    human = None
+    if _wants_human(scfg, s2, human_poses) and points.shape[0] > 0:
+        human = human_light(nets, points, normals, view_dirs, m_raw, human_poses)
+    diffuse_light, light, light0, occ, indirect = lights(nets, exp_max, points, n, refl, rough, sphere, detail=True, pos_freq=pos_freq,
+                                                         human=human)
     t = torch.clamp(1 - nov, 0.0, 1.0)
     fres = torch.clamp(0.04 + 0.96 * t * t * t * t * t, 0.0, 1.0)
     fg = G.lut_bilinear_clamp(lut[0], torch.cat([torch.clamp(nov, 0.0, 1.0), torch.clamp(rough, 0.0, 1.0)], -1))
@@ -142,5 +180,7 @@ def _shade_with_images(nets, scfg, lut, points, normals, view_dirs, feats, s2, i
         'refraction_light': c01(G.linear_to_srgb((1 - fres) * refrac * trans)),
         'reflection_weight': fres,
     }
+    if human is not None:          # field.py:773-774
+        inter['human_light'] = G.linear_to_srgb(human[0] * human[1])
     occ_info = {'reflective': refl, 'occ_prob': occ, 'transmission_weight': trans, 'metallic': metallic}
     return color, occ_info, inter

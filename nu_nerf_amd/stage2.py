@@ -46,6 +46,15 @@ class IoRNetwork(nn.Module):
         raise RuntimeError("IoRNetwork is a parameter holder: evaluate it through its Stage2Renderer (nets().ior / .thickness)")
 
 
+def inner_shading_network(cls, shader_config):
+    """The inner surface's shading module of a stage-2 renderer.  shader_config.human_light is a stage-1 feature: the
+    stage-2 shading has no camera poses to take human frames from, so the key is refused at construction, as it always was."""
+    if {**cls.default_cfg, **shader_config}['human_light']:
+        raise NotImplementedError("human_light=True is built for the stage-1 renderers only (network: shape): the stage-2 inner shading "
+                                  "network does not support it")
+    return cls(shader_config)
+
+
 class AppShadingNetworkS2(nn.Module):
     """Holds no parameters of its own; keeps the stage-1 network as a child like the reference (field.py:798-802), which is
     what puts the `color_network.stage1_network.*` aliases into state_dict()."""
@@ -108,7 +117,7 @@ class Stage2Renderer(nn.Module):
         self.color_network = AppShadingNetworkS2(self.cfg['shader_config'], self.stage1_network)
         self.sdf_network_inner = SDFNetwork()
         self.deviation_network_inner = SingleVarianceNetwork(self.cfg['inv_s_init'])
-        self.color_network_inner = AppShadingNetwork(self.cfg['shader_config'])
+        self.color_network_inner = inner_shading_network(AppShadingNetwork, self.cfg['shader_config'])
         self._init_own_parameters()
         self._mesh = self._load_mesh()
         self.scene = None

@@ -363,6 +363,91 @@ def shade_combine(eng, m_raw, ol_raw, il_raw, iw_raw, rl_raw, nov, lut, exp_max,
     return _ShadeCombineFn.apply(eng, m_raw, ol_raw, il_raw, iw_raw, rl_raw, nov, lut.contiguous(), float(exp_max), bool(s2), bool(internal))
 
 
+class _HumanEncodeFn(torch.autograd.Function):
+    """Input rows of human_light_predictor (nu_human_encode_*, field.py:411-445, :618-629) for explicit points / normals / view
+    directions with one human frame per point.  Gradients: the raw normal and the roughness logit; points, view directions and poses
+    carry none (they are constants of a stage-1 step)."""
+
+    @staticmethod
+    def forward(ctx, eng, x, nrm, view, m_raw, poses):
+        x, nrm, view, m, poses = (t.detach().to(torch.float32).contiguous() for t in (x, nrm, view, m_raw, poses))
+        P, dev = x.shape[0], x.device
+        if tuple(poses.shape) != (P, 3, 4):
+            raise ValueError(f"human_encode: poses must be [{P},3,4] (one human frame per point), got {tuple(poses.shape)}")
+        pt = torch.zeros(P, 8, device=dev)          # point records as render_core holds them: x, -, ray direction = -view
+        pt[:, :3] = x
+        pt[:, 4:7] = -view
+        idx = torch.arange(P, dtype=torch.int32, device=dev)
+        HL, rec = torch.empty(P, eng.ld_hl, device=dev), torch.empty(P, 4, device=dev)
+        eng.lib.nu_human_encode_fwd(addr(nrm), addr(pt), 8, addr(m), m.shape[1], addr(idx), 1, addr(poses), P, P, eng.ld_hl,
+                                    addr(HL), addr(rec), eng.stream())
+        ctx.eng, ctx.mcols = eng, m.shape[1]
+        ctx.save_for_backward(nrm, pt, m, idx, poses, rec)
+        ctx.mark_non_differentiable(rec)
+        ctx.set_materialize_grads(False)
+        return HL, rec
+
+    @staticmethod
+    def backward(ctx, dHL, _drec):
+        nrm, pt, m, idx, poses, rec = ctx.saved_tensors
+        P, dev, eng = nrm.shape[0], nrm.device, ctx.eng
+        dn, dm = torch.zeros(P, 3, device=dev), torch.zeros(P, ctx.mcols, device=dev)
+        if dHL is not None and P > 0:
+            dHL = dHL.contiguous()
+            eng.lib.nu_human_encode_bwd(addr(nrm), addr(pt), 8, addr(m), ctx.mcols, addr(idx), 1, addr(poses), P, addr(rec), addr(dHL),
+                                        eng.ld_hl, P, addr(dn), addr(dm), ctx.mcols, eng.stream())
+        return None, None, dn, None, dm, None
+
+
+def human_encode(eng, x, nrm, view, m_raw, poses):
+    """-> (HLin [P, eng.ld_hl]: the 24 IPE columns of the human-light predictor and zero padding, rec [P,4]: hit flag, dist, mean)."""
+    return _HumanEncodeFn.apply(eng, x, nrm, view, m_raw, poses)
+
+
+class _ShadeCombineHLFn(torch.autograd.Function):
+    """_ShadeCombineFn's stage-1 form with the human-light blend (nu_shade_combine_hl_*): second output h w | w [P,4] (no gradient:
+    it feeds the validation image only)."""
+
+    @staticmethod
+    def forward(ctx, eng, m_raw, ol_raw, il_raw, iw_raw, rl_raw, hl_raw, rec, nov, lut, exp_max):
+        P, dev = m_raw.shape[0], m_raw.device
+        pad = lambda t, rows, w: torch.cat([t.detach(), torch.zeros(rows, w - t.shape[1], device=dev)], 1).contiguous()
+        Mraw, OLo, ILo, RLo, HLo = pad(m_raw, P, 8), pad(ol_raw, 3 * P, 4), pad(il_raw, 2 * P, 4), pad(rl_raw, P, 4), pad(hl_raw, P, 4)
+        IWo = iw_raw.detach().reshape(P).contiguous()
+        rec = rec.detach().contiguous()
+        SD = torch.zeros(P, 8, device=dev)
+        SD[:, 3] = nov.detach().reshape(P)
+        idx = torch.arange(P, dtype=torch.int32, device=dev)
+        color, hw = torch.empty(P, 4, device=dev), torch.empty(P, 4, device=dev)
+        eng.lib.nu_shade_combine_hl_fwd(addr(Mraw), 8, addr(OLo), addr(ILo), addr(IWo), addr(RLo), addr(HLo), addr(rec), addr(SD), addr(lut),
+                                        addr(idx), P, exp_max, addr(color), None, addr(hw), eng.stream())
+        ctx.eng, ctx.exp_max, ctx.bufs = eng, exp_max, (Mraw, OLo, ILo, IWo, RLo, HLo, rec, SD, idx, lut)
+        ctx.mark_non_differentiable(hw)
+        ctx.set_materialize_grads(False)
+        return color[:, :3].contiguous(), hw
+
+    @staticmethod
+    def backward(ctx, dcolor, _dhw):
+        eng = ctx.eng
+        Mraw, OLo, ILo, IWo, RLo, HLo, rec, SD, idx, lut = ctx.bufs
+        P, dev = Mraw.shape[0], Mraw.device
+        dc4 = torch.zeros(P, 4, device=dev)
+        if dcolor is not None:
+            dc4[:, :3] = dcolor
+        z = torch.zeros_like
+        dMraw, dOLo, dILo, dIWo, dRLo, dHLo, dNoV = z(Mraw), z(OLo), z(ILo), z(IWo), z(RLo), z(HLo), torch.zeros(P, device=dev)
+        eng.lib.nu_shade_combine_hl_bwd(addr(Mraw), 8, addr(OLo), addr(ILo), addr(IWo), addr(RLo), addr(HLo), addr(rec), addr(SD), addr(lut),
+                                        addr(idx), P, ctx.exp_max, addr(dc4), addr(dMraw), addr(dOLo), addr(dILo), addr(dIWo), addr(dRLo),
+                                        addr(dHLo), addr(dNoV), eng.stream())
+        return None, dMraw[:, :6], dOLo[:, :3], dILo[:, :3], dIWo[:, None], dRLo[:, :3], dHLo, None, dNoV[:, None], None, None
+
+
+def shade_combine_hl(eng, m_raw, ol_raw, il_raw, iw_raw, rl_raw, hl_raw, rec, nov, lut, exp_max):
+    """shade_combine (stage-1 form) with the raw human-light heads hl_raw [P,4] and the encoder's record rec [P,4]
+    -> (sRGB colour [P,3], [P,4] = h w | w)."""
+    return _ShadeCombineHLFn.apply(eng, m_raw, ol_raw, il_raw, iw_raw, rl_raw, hl_raw, rec, nov, lut.contiguous(), float(exp_max))
+
+
 class _NeusAlphaFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, eng, sdf, nrm, dirs, dist, inv_s, ca):

@@ -27,7 +27,7 @@ from .lbvh import Scene, dintersect_hip
 from .nets import Stage1Nets
 from .renderer import AppShadingNetwork, NeRFNetwork, SDFNetwork, SingleVarianceNetwork
 from .renderer_std import NeROShapeRenderer
-from .stage2 import AppShadingNetworkS2, IoRNetwork
+from .stage2 import AppShadingNetworkS2, IoRNetwork, inner_shading_network
 from .stage2 import Stage2Renderer as _ZeroThickStage2
 
 
@@ -60,7 +60,7 @@ class Stage2Renderer(_ZeroThickStage2):
         self.color_network = AppShadingNetworkS2(self.cfg['shader_config'], self.stage1_network)
         self.sdf_network_inner = SDFNetwork()
         self.deviation_network_inner = SingleVarianceNetwork(self.cfg['inv_s_init'])
-        self.color_network_inner = AppShadingNetworkSpecInner(self.cfg['shader_config'])
+        self.color_network_inner = inner_shading_network(AppShadingNetworkSpecInner, self.cfg['shader_config'])
         self._init_own_parameters()
         self._mesh = self._load_mesh()
         self.scene = None

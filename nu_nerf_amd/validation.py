@@ -25,7 +25,7 @@ def composite_weights(eng, ctx):
 
 
 @torch.no_grad()
-def compute_validation_info(renderer, z_vals, rays_o, rays_d, weights, step):
+def compute_validation_info(renderer, z_vals, rays_o, rays_d, weights, step, human_poses=None):
     eng = renderer.engine()
     nets = Stage1Nets(eng, renderer._named())
     depth = torch.sum(weights * z_vals, -1, keepdim=True)
@@ -36,7 +36,7 @@ def compute_validation_info(renderer, z_vals, rays_o, rays_d, weights, step):
     out = {'depth': depth, 'normal': ((F.normalize(grads, dim=-1) + 1.0) * 0.5) * inner}
     scfg = renderer.color_network.cfg
     _, occ_info, inter = shade(nets, scfg, renderer.color_network.FG_LUT, points, grads, -F.normalize(rays_d, dim=-1),
-                               y[:, 1:], inter_results=True)
+                               y[:, 1:], inter_results=True, human_poses=human_poses if scfg.get('human_light', False) else None)
     # get_intersection(sn0=128, sn1=9): points with |x| >= 0.999 keep zero weights (field.py:533-553)
     inside = torch.nonzero(torch.norm(points, dim=-1) < 0.999)[:, 0]
     occ_gt = torch.zeros(points.shape[0], 1, device=points.device)
@@ -59,15 +59,17 @@ def render_eval(renderer, batch, step, chunk=None):
     chunks of cfg['test_ray_num'] rays, no jitter, cos_anneal 0, is_train=False."""
     trn = int(chunk or renderer.cfg['test_ray_num'])
     is_nerf = renderer.cfg['is_nerf']
-    outs = {k: [] for k in _EVAL_KEYS}
+    keys = _EVAL_KEYS + (['human_light'] if renderer.color_network.cfg.get('human_light', False) else [])
+    outs = {k: [] for k in keys}
     n = batch['rays_o'].shape[0]
     for ri in range(0, n, trn):
         cur = {k: v[ri:ri + trn] for k, v in batch.items()}
         rays_o, rays_d, near, far, hp = renderer._process_nerf_ray_batch(cur)
+        hp = cur.get('human_poses')          # real captures with shader_config.human_light: the rays' human frames [n,3,4]
         if not is_nerf:         # real captures: near / far bracket the unit sphere (renderer_zerothick.py:357)
             near, far = renderer.near_far_from_sphere(rays_o, rays_d)
         o = renderer.render(rays_o, rays_d, near, far, hp, 0, 0, is_train=False, step=step, is_nerf=is_nerf)
-        for k in _EVAL_KEYS:
+        for k in keys:
             outs[k].append(o[k].detach())
     outs = {k: torch.cat(v, 0) for k, v in outs.items()}
     if 'rgbs' in batch:
