@@ -679,6 +679,25 @@ int nu_bake_net_size(void);
 int nu_material_bake_fwd(const NuBakeNet* net, const float* X, int x_ld, int P, float* metallic, float* roughness, float* albedo,
                          float* transmission, float* sdf, hipStream_t stream);
 
+/* The illumination the shading network learned, for a caller's directions, as ONE fully-fused no-gradient kernel (csrc/light_bake.hip;
+ * predict_specular_lights with reflective = d and no human light, network/field.py:636-667, :1399-1430).  Row p = (direction
+ * dirs[p] [N,3], roughness kinv[p] = the kappa_inv of nu_ide, point): x == NULL is the origin for every row, x_stride == 0 the one
+ * point x[0..2] for every row, otherwise row p reads x + p * x_stride (x_stride >= 3).
+ *   probe == 0: light = direct = exp(min(outer_light([IDE(d, rho) | IDE(sph(x, d), rho) if net->sphere]), exp_max)); the input row is
+ *               the one nu_spec_encode writes (net->ld_ol columns) at the row's roughness.
+ *   probe != 0 (needs x): indirect = exp(min(inner_light([pos_enc(x) | IDE(d, rho)]), exp_max)) * occ,
+ *               occ = clamp(0.5 inner_weight([pos_enc(x) | dir_enc(d)]) + 0.5, 0, 1), light = indirect + direct (1 - occ); pos_enc has
+ *               pos_freq <= 8 frequencies, the input rows are ILin / IWin of nu_s2_shade_encode_fwd.
+ *   light, direct, indirect [N,3]; occ [N]; every output pointer may be NULL.  Exact fp32 in the k order of the layered path
+ *   (nu_gemm_nt + nu_skinny_fwd): the raw heads are bit-identical to it.  It reads the fp32 packed tables only.
+ *   Test outputs: enc_dbg [N, ld_ol (+ 128 + 96 with probe)] the encoded rows, raw_dbg [N,8] the heads before their activations
+ *   (direct 3, indirect 3, occlusion 1, 0).
+ *   NU_ERR_ARG: net / dirs / kinv NULL, N < 0, probe without x, 0 < x_stride < 3, tables that are not the 3 x 256 predictors.
+ *   N == 0 launches nothing. */
+int nu_light_bake_fwd(const NuShadeNet* net, const float* dirs, const float* kinv, const float* x, int x_stride, int pos_freq, int N,
+                      int probe, float* light, float* direct, float* indirect, float* occ, float* enc_dbg, float* raw_dbg,
+                      hipStream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * Fused loss assembly: from the renderer's per-ray outputs to the scalar the trainer back-propagates, for
  * the loss set of the shipped stage-1 configs -- white background + clamp (renderer_zerothick.py:783-787), charbonier RGB

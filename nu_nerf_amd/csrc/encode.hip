@@ -8,23 +8,11 @@
 //   shading directions n^, v^, r = 2(v.n)n - v, NoV              network/field.py:686-689
 //   NeRF++ inputs (x/|x|, 1/|x|), view = -d                      network/renderer_zerothick.py:687-690
 #include "nu_common.h"
-#include "ide_table.h"
+#include "ide.h"
 
 // Per-point record written by the partition kernel (render.hip): 8 floats
 //   [0..2] position x, [3] dist (section length), [4..6] unit ray direction d, [7] unused
 #define NU_PT 8
-
-// column -> (is_raw, k, coord, is_cos) for an L-frequency embedding of a D-vector:
-// col < D : x[col];  else q = col - D, k = q / (2D), r = q % (2D), c = r % D, cos if r >= D
-static __device__ inline float nu_embed_col(const float* x, int D, int col) {
-    if (col < D) return x[col];
-    const int q = col - D;
-    const int k = q / (2 * D);
-    const int r = q - k * 2 * D;
-    const int c = r >= D ? r - D : r;
-    const float a = x[c] * (float)(1 << k);
-    return r >= D ? cosf(a) : sinf(a);
-}
 
 // ------------------------------------------------------------------------------------------------
 // SDF inputs:  E[p, 0:39] (+ zero pad to 64),  U4[p, 217:256] = embedding,  YX[p, 257:260] = x, rest of YX pad = 0
@@ -130,66 +118,6 @@ extern "C" int nu_embed_j(const float* E, const float* nbar, int P, float* Q0, f
     return nu_launch_status();
 }
 
-// ------------------------------------------------------------------------------------------------
-// IDE: lane i < 36 evaluates term i.  Returns (re, im) and optionally the partials.
-// ------------------------------------------------------------------------------------------------
-// Per-lane constants of term i = lane (loaded once per kernel: the Horner loop then runs out of registers with a uniform
-// trip count -- coefficients above degree l - m are zero in the table, and leading zeros leave Horner's arithmetic unchanged)
-struct NuIdeLane {
-    float c[NU_IDE_DEG];
-    float sigma, att1;     // l(l+1)/2 and exp(-sigma) (kappa_inv = 1: the diffuse query)
-    int m;
-    bool live;
-};
-static __device__ inline NuIdeLane nu_ide_lane(int lane) {
-    NuIdeLane L;
-    const int i = lane < NU_IDE_TERMS ? lane : NU_IDE_TERMS - 1;
-#pragma unroll
-    for (int k = 0; k < NU_IDE_DEG; ++k) L.c[k] = c_ide_mat[i][k];
-    const int l = c_ide_l[i];
-    L.m = c_ide_m[i];
-    L.sigma = 0.5f * (float)l * (float)(l + 1);
-    L.att1 = expf(-L.sigma);
-    L.live = lane < NU_IDE_TERMS;
-    return L;
-}
-// Direction-dependent factors of one term, shared by every kappa the direction is queried with
-struct NuIdeDir {
-    float are, aim;        // (x+iy)^m
-    float pre, pim;        // (x+iy)^(m-1)   (0 for m = 0)
-    float poly, dpoly;     // P(z), P'(z)
-};
-static __device__ inline NuIdeDir nu_ide_dir(const NuIdeLane& L, float x, float y, float z) {
-    NuIdeDir t;
-    float ar = 1.f, ai = 0.f, pr = 0.f, pi = 0.f;
-#pragma unroll
-    for (int j = 0; j < NU_IDE_DEG - 1; ++j) {
-        if (j < L.m) {
-            pr = ar; pi = ai;
-            const float nr = ar * x - ai * y;
-            const float ni = ar * y + ai * x;
-            ar = nr; ai = ni;
-        }
-    }
-    float poly = 0.f, dpoly = 0.f;
-#pragma unroll
-    for (int k = NU_IDE_DEG - 1; k >= 0; --k) {
-        dpoly = dpoly * z + poly;
-        poly = poly * z + L.c[k];
-    }
-    t.are = ar; t.aim = ai; t.pre = pr; t.pim = pi; t.poly = poly; t.dpoly = dpoly;
-    return t;
-}
-static __device__ inline float nu_ide_att(const NuIdeLane& L, float kinv) { return expf(-L.sigma * kinv); }
-
-// write one 72-d IDE row (+ zero pad up to `padto` columns) given the direction factors and the attenuation
-static __device__ inline void nu_ide_store(float* row, int lane, const NuIdeLane& L, const NuIdeDir& t, float att, int padto) {
-    if (L.live) {
-        row[lane] = t.are * t.poly * att;
-        row[36 + lane] = t.aim * t.poly * att;
-    }
-    for (int c = 72 + lane; c < padto; c += 64) row[c] = 0.f;
-}
 // per-lane partials of d/d(x, y, z) of sum_i (gre_i re_i + gim_i im_i) for gradient weights already scaled by the
 // attenuation (gre, gim = sum over rows of att_row * g_row)
 static __device__ inline void nu_ide_dir_grad(const NuIdeLane& L, const NuIdeDir& t, float gre, float gim, float& ax, float& ay,
@@ -274,32 +202,6 @@ static __device__ inline void nu_shade_dirs(const float* n, const float* d, floa
     for (int c = 0; c < 3; ++c) r[c] = nov * nh[c] * 2.0f - vh[c];
 }
 
-// Point on the unit sphere seen from p (inside, moved to radius 0.999 when outside) along `dir`
-// (offset_points_to_sphere + get_sphere_intersection + normalize; field.py:447-464, :642-643, :676-677)
-struct NuSph {
-    float s[3];       // unit point on the sphere
-    float pp[3];      // offset origin p'
-    float t, root, snorm;
-};
-static __device__ inline NuSph nu_sph_point(const float* x, const float* dir) {
-    NuSph o;
-    const float xn = sqrtf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-    const float sc = xn > 0.999f ? 0.999f / xn : 1.0f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) o.pp[c] = xn > 0.999f ? x[c] / xn * 0.999f : x[c];
-    (void)sc;
-    const float b = o.pp[0] * dir[0] + o.pp[1] * dir[1] + o.pp[2] * dir[2];
-    const float cc = o.pp[0] * o.pp[0] + o.pp[1] * o.pp[1] + o.pp[2] * o.pp[2];
-    o.root = sqrtf(b * b - cc + 1.0f + 1e-6f);
-    o.t = -b + o.root;
-    float sv[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) sv[c] = o.pp[c] + dir[c] * o.t;
-    o.snorm = fmaxf(sqrtf(sv[0] * sv[0] + sv[1] * sv[1] + sv[2] * sv[2]), 1e-12f);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) o.s[c] = sv[c] / o.snorm;
-    return o;
-}
 // cotangent of the unit sphere point -> cotangent of dir
 static __device__ inline void nu_sph_point_bwd(const NuSph& o, const float* dir, const float* ds_unit, float* ddir) {
     const float dotp = ds_unit[0] * o.s[0] + ds_unit[1] * o.s[1] + ds_unit[2] * o.s[2];

@@ -735,6 +735,20 @@ class Stage1Engine:
         self.lib.nu_material_bake_fwd(ctypes.byref(n), X, x_ld, P, addr(metallic), addr(roughness), addr(albedo), addr(transmission),
                                       addr(sdf), self.stream())
 
+    # ------------------------------------------------------------------ light bake
+    def light_bake(self, dirs, kinv, N, x=None, x_stride=0, *, probe=False, light=None, direct=None, indirect=None, occ=None, enc=None,
+                   raw=None):
+        """The learned illumination at N rows in ONE kernel (csrc/light_bake.hip).  dirs [N,3], kinv [N] (roughness = the IDE's kappa_inv),
+        x: None (the origin), one point (x_stride 0) or a point per row (x_stride floats apart); fp32 device tensors.  Written to the
+        fp32 tensors given (None: not written): light, direct, indirect [N,3] and occ [N]; probe=True also evaluates inner_light /
+        inner_weight with this engine's light_pos_freq (needs x).  Reads the fp32 packed tables, which pack() writes in every
+        mlp_dtype.  enc [N, ld_ol (+ 224 with probe)] / raw [N,8]: the kernel's test outputs (encoded rows; heads before activation)."""
+        if self._desc_dev is None or self._ptr_sig != self._signature():
+            self._upload_descs()
+        self.lib.nu_light_bake_fwd(ctypes.byref(self._shade_net), addr(dirs), addr(kinv), addr(x), x_stride, self.light_pos_freq, N,
+                                   1 if probe else 0, addr(light), addr(direct), addr(indirect), addr(occ), addr(enc), addr(raw),
+                                   self.stream())
+
     # ------------------------------------------------------------------ SDF network
     def sdf_forward(self, X, x_ld, P, *, keep=True, want_feat=True):
         """SDF MLP forward on P points (X: device address of [P, x_ld] rows whose first 3 floats are x).

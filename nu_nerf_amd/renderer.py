@@ -332,6 +332,12 @@ class NeROShapeRenderer(nn.Module):
         from .materials import predict_materials
         return predict_materials(self, mesh)
 
+    def predict_environment(self, h=256, w=512, roughness=0.0, point=None, probe=False):
+        """The illumination the model learned as a lat-long map, float32 numpy [h,w,3] ([L,h,w,3] for a sequence of roughness values) in
+        relight's convention, baked by one fused kernel (environment.py)."""
+        from .environment import predict_environment
+        return predict_environment(self, h, w, roughness, point, None, probe)
+
     # ---- data ----------------------------------------------------------------------------------
     def _init_dataset(self):
         """Ray-batch store (renderer_zerothick.py:167-190).  `database_name: synthetic/<n_rays>` builds the seeded synthetic
