@@ -608,6 +608,16 @@ int nu_sdf_fused_fwd(const NuSdfNet* net, const float* X, int x_ld, int P, float
 /* the same in the bf16-STORAGE arithmetic (NuOpCtx.h16: bf16 weight tables NuLin.Wp16, activations rounded to bf16 between layers,
  * v_mfma_f32_32x32x16_bf16 with fp32 accumulation): bit-identical to nu_sdf_mlp_fwd(..., want_feat = 0) under h16 */
 int nu_sdf_fused16_fwd(const NuSdfNet* net, const float* X, int x_ld, int P, float* sdf, hipStream_t stream);
+/* The second-order jet of the SDF as ONE fully-fused no-gradient kernel (csrc/sdf_jet.hip): value, gradient and Hessian in forward mode
+ * (ten rows per point through the pipeline of nu_sdf_fused_fwd, exact fp32 on the fp32 packed tables in every mlp_dtype), and from them
+ * the curvatures of the level set through each point, with g = grad f, H = Hessian f:
+ *   mean = (|g|^2 tr H - g^T H g) / (2 |g|^3),  gauss = g^T adj(H) g / |g|^4,  normal = g / |g|     (f = |x| - r: 1 / r, 1 / r^2)
+ * Where |g|^2 < 1e-12: mean = gauss = 0, normal = 0.
+ *   X [P, x_ld] (x = the first three floats of a row, x_ld >= 3); sdf [P] (the bits of nu_sdf_fused_fwd), grad [P,3], hess [P,6] in the
+ *   order xx, yy, zz, xy, xz, yz; mean, gauss [P]; normal [P,3].  Every output pointer may be NULL.  No workspace.
+ *   NU_ERR_ARG: net or X NULL, P < 0, x_ld < 3.  P == 0 launches nothing. */
+int nu_sdf_jet_fwd(const NuSdfNet* net, const float* X, int x_ld, int P, float* sdf, float* grad, float* hess, float* mean,
+                   float* gauss, float* normal, hipStream_t stream);
 int nu_sdf_mlp_normal(NuOpCtx* ctx, const NuSdfNet* net, NuSdfBufs* bufs, hipStream_t stream);
 int nu_sdf_mlp_bwd(NuOpCtx* ctx, const NuSdfNet* net, NuSdfBufs* bufs, const float* dYX, const float* nbar, float* dx,
                    hipStream_t stream);

@@ -735,6 +735,17 @@ class Stage1Engine:
         self.lib.nu_material_bake_fwd(ctypes.byref(n), X, x_ld, P, addr(metallic), addr(roughness), addr(albedo), addr(transmission),
                                       addr(sdf), self.stream())
 
+    # ------------------------------------------------------------------ SDF jet (curvature)
+    def sdf_jet(self, X, x_ld, P, sdf=None, grad=None, hess=None, mean=None, gauss=None, normal=None):
+        """Value, gradient and Hessian of the SDF network at P points (X: device address of [P, x_ld] rows whose first 3 floats are x) and
+        the curvatures of its level sets, in ONE no-gradient kernel (csrc/sdf_jet.hip: the second-order jet in forward mode), written to
+        the fp32 tensors given (sdf, mean, gauss [P]; grad, normal [P,3]; hess [P,6] = xx, yy, zz, xy, xz, yz; None: not written).  No
+        workspace.  Reads the fp32 packed tables, which pack() writes in every mlp_dtype."""
+        if self._desc_dev is None or self._ptr_sig != self._signature():
+            self._upload_descs()
+        self.lib.nu_sdf_jet_fwd(ctypes.byref(self._sdf_net), X, x_ld, P, addr(sdf), addr(grad), addr(hess), addr(mean), addr(gauss),
+                                addr(normal), self.stream())
+
     # ------------------------------------------------------------------ light bake
     def light_bake(self, dirs, kinv, N, x=None, x_stride=0, *, probe=False, light=None, direct=None, indirect=None, occ=None, enc=None,
                    raw=None):

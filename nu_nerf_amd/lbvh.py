@@ -132,16 +132,33 @@ def vertex_normals_and_curvature(Vc, Fc):
     return normals, curv
 
 
+def check_vertex_curvature(curvature, n_verts):
+    """A caller's per-vertex Gaussian curvature ([V] or [V,1], tensor or array) -> float32 [V,1] clipped to [-10, 10] (DiffRender.py:360);
+    ValueError when the shape is another or a value is not finite."""
+    c = torch.as_tensor(curvature).detach().to(torch.float32)
+    if tuple(c.shape) not in ((n_verts,), (n_verts, 1)):
+        raise ValueError(f"curvature must be [{n_verts}] or [{n_verts},1] (one value per vertex), got {tuple(c.shape)}")
+    if not bool(torch.isfinite(c).all()):
+        raise ValueError("curvature must be finite")
+    return torch.clamp(c.reshape(n_verts, 1), -10.0, 10.0).contiguous()
+
+
 class Scene:
     """Triangle mesh + LBVH with the reference Scene's tracing surface (DiffRender.py:318-360, :539-549)."""
 
-    def __init__(self, vertices, faces):
+    def __init__(self, vertices, faces, curvature=None):
+        """curvature: None = the angle-defect curvature of vertex_normals_and_curvature; a [V] / [V,1] tensor replaces it (finite;
+        clipped to [-10, 10] as DiffRender.py:360 clips PyMesh's), e.g. curvature.bake_curvature(...)['gaussian']."""
         self.vertices = vertices.detach().to(torch.float32).contiguous()
         self.faces = faces.detach().to(torch.long).contiguous()
-        self.bvh = LBVH(self.vertices, self.faces)
         dev = self.vertices.device
+        if curvature is not None:
+            curvature = check_vertex_curvature(curvature, int(self.vertices.shape[0])).to(dev)
+        self.bvh = LBVH(self.vertices, self.faces)
         normals, curv = vertex_normals_and_curvature(self.vertices.cpu(), self.faces.cpu())
         self.normals, self.gaussian_curvatures = normals.to(dev), curv.to(dev)
+        if curvature is not None:
+            self.gaussian_curvatures = curvature
 
     def intersect(self, origin, direction):
         hit, idx = self.bvh.intersect(torch.cat([origin, direction], 1))

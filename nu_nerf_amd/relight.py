@@ -1,5 +1,5 @@
 """python -m nu_nerf_amd.relight --mesh PLY --material DIR --hdr FILE --name NAME [--trans] [--num 360 --width 800 --height 800
---samples 1024 --cam_dist 3.0 --azimuth 0 --elevation 45] [--inner PLY --inner-material DIR (--ior VALUE_OR_DIR | --shell DIR_OR_PAIR)]
+--samples 1024 --cam_dist 3.0 --azimuth 0 --elevation 45] [--inner PLY --inner-material DIR (--ior VALUE_OR_DIR | --shell DIR_OR_PAIR [--shell-curvature FILE])]
 
 relight.py + blender_backend/relight_backend.py on the GPU: the extracted mesh, the per-vertex DIR/metallic.npy, roughness.npy and
 albedo.npy that extract_materials writes and a lat-long HDR environment map are rendered from the reference's camera orbit
@@ -564,6 +564,8 @@ def parse_args(argv=None):
                     help="index of refraction of the shell: a number (default 1.5) or a directory with ior.npy [V,1]")
     ap.add_argument('--shell', type=str, default=None,
                     help="thin glass shell instead of --ior: a directory with shell_ior.npy and shell_thickness.npy [V,1], or \"IOR,THICKNESS\"")
+    ap.add_argument('--shell-curvature', dest='shell_curvature', type=str, default=None,
+                    help="with --shell: curvature.npy [V,1] of the shell's vertices (extract_curvature) instead of the mesh's angle defect")
     ap.add_argument('--output', type=str, default=None, help="output directory (default data/relight/NAME)")
     ap.add_argument('--width', type=int, default=800)
     ap.add_argument('--height', type=int, default=800)
@@ -583,6 +585,8 @@ def parse_args(argv=None):
         ap.error("--num, --width, --height and --chunk must be >= 1")
     if flags.shell is not None and flags.ior is not None:
         ap.error("--shell and --ior exclude each other: the shell is either the thin wall or solid glass")
+    if flags.shell_curvature is not None and flags.shell is None:
+        ap.error("--shell-curvature needs --shell")
     if flags.ior is None:
         flags.ior = '1.5'
     if flags.inner is None:
@@ -644,6 +648,15 @@ def load_shell(spec, n_verts):
     return tuple(load_ior(v, n_verts) for v in spec)
 
 
+def load_shell_curvature(path, n_verts):
+    """--shell-curvature: float32 [n_verts] of a curvature.npy as extract_curvature writes it, clipped to [-10, 10] like the curvature the
+    stage-2 model trains with (lbvh.Scene)."""
+    a = np.load(path)
+    if a.size != n_verts or a.shape not in ((n_verts,), (n_verts, 1)):
+        raise ValueError(f"{path}: expected [{n_verts},1] (one curvature per vertex of the shell), got {a.shape}")
+    return np.clip(np.ascontiguousarray(a, np.float32).reshape(-1), -10.0, 10.0)
+
+
 def output_dir(flags):
     return flags.output or os.path.join('data', 'relight', flags.name)
 
@@ -681,7 +694,8 @@ def main(argv=None):
             Vi = (np.asarray(Vi, np.float64) @ TRANS.T).astype(np.float32)
         if flags.shell is not None:
             ior, thickness = load_shell(parse_shell(flags.shell), len(V))
-            scene = ThinShellScene(V, F, ior, thickness, Vi, Fi, load_materials(flags.inner_material))
+            curvature = None if flags.shell_curvature is None else load_shell_curvature(flags.shell_curvature, len(V))
+            scene = ThinShellScene(V, F, ior, thickness, Vi, Fi, load_materials(flags.inner_material), curvature=curvature)
         else:
             scene = NestedScene(V, F, load_ior(parse_ior(flags.ior), len(V)), Vi, Fi, load_materials(flags.inner_material))
     env = read_hdr(flags.hdr)

@@ -332,6 +332,12 @@ class NeROShapeRenderer(nn.Module):
         from .materials import predict_materials
         return predict_materials(self, mesh)
 
+    def predict_curvature(self, mesh=None):
+        """{'gaussian' [V,1], 'mean' [V], 'normal' [V,3]} (float32 numpy) of the SDF's zero set at the vertices of `mesh` (as
+        predict_materials reads it), from the SDF's Hessian by one fused kernel (curvature.py)."""
+        from .curvature import predict_curvature
+        return predict_curvature(self, mesh)
+
     def predict_environment(self, h=256, w=512, roughness=0.0, point=None, probe=False):
         """The illumination the model learned as a lat-long map, float32 numpy [h,w,3] ([L,h,w,3] for a sequence of roughness values) in
         relight's convention, baked by one fused kernel (environment.py)."""

@@ -212,6 +212,12 @@ class Stage2Renderer(nn.Module):
         from .materials import predict_materials
         return predict_materials(self, mesh, which)
 
+    def predict_curvature(self, mesh=None, which='inner'):
+        """Curvature of an SDF of the model at the vertices of `mesh` (curvature.py): which='inner' sdf_network_inner, which='outer' the
+        stage-1 SDF."""
+        from .curvature import predict_curvature
+        return predict_curvature(self, mesh, which)
+
     def predict_environment(self, h=256, w=512, roughness=0.0, point=None, which='outer', probe=False):
         """The illumination the model learned as a lat-long map (environment.py): which='outer' (the default: the environment is the
         outer light) evaluates the stage-1 networks the model carries, which='inner' the light predictors of color_network_inner."""

@@ -42,11 +42,22 @@ class AppShadingNetworkSpecInner(AppShadingNetwork):
 
 
 class Stage2Renderer(_ZeroThickStage2):
-    default_cfg = {**NeROShapeRenderer.default_cfg, 'train_ray_num': 1024, 'is_nerf': False}
+    # shell_curvature: where the Gaussian curvature of the shell's two spheres comes from.  'mesh' (the reference's choice: a discrete
+    # curvature of the stage-1 mesh; here the angle defect of lbvh.py) or 'sdf' (this project's own: the stage-1 SDF's curvature at the
+    # mesh vertices, curvature.py)
+    default_cfg = {**NeROShapeRenderer.default_cfg, 'train_ray_num': 1024, 'is_nerf': False, 'shell_curvature': 'mesh'}
+    SHELL_CURVATURE = ('mesh', 'sdf')
+
+    @classmethod
+    def check_shell_curvature(cls, value):
+        if value not in cls.SHELL_CURVATURE:
+            raise ValueError(f"shell_curvature={value!r}: expected 'mesh' or 'sdf'")
+        return value
 
     def __init__(self, cfg, training=True):
         nn.Module.__init__(self)
         self.cfg = {**self.default_cfg, **cfg}
+        self.check_shell_curvature(self.cfg['shell_curvature'])
         self.is_nerf = self.cfg['is_nerf']
         self.get_mask = self.cfg['get_mask']                           # renderer.py:962 (default False here; the reference has no default)
         self.IORs = nn.Parameter(torch.zeros(10))
@@ -128,7 +139,14 @@ class Stage2Renderer(_ZeroThickStage2):
             ecfg.update(self.color_network_inner.cfg)
             n2 = Stage1Nets(Stage1Engine(named, dev, ecfg), named)
             V, Fc = self._mesh
-            self.scene = Scene(torch.from_numpy(V).to(dev), torch.from_numpy(Fc).to(dev))
+            Vd = torch.from_numpy(V).to(dev)
+            curv = None
+            if self.cfg['shell_curvature'] == 'sdf':
+                # the curvature of the surface the mesh was extracted from: the stage-1 SDF's own, from its Hessian at the vertices
+                # (curvature.py), once; Scene clips it to [-10, 10] like the mesh curvature
+                from .curvature import bake_curvature
+                curv = bake_curvature(self, Vd.to(torch.float32).contiguous(), which='outer')['gaussian']
+            self.scene = Scene(Vd, torch.from_numpy(Fc).to(dev), curvature=curv)
             self._nets = (n1, n2)
         return self._nets
 
