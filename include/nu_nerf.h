@@ -618,6 +618,26 @@ int nu_sdf_fused16_fwd(const NuSdfNet* net, const float* X, int x_ld, int P, flo
  *   NU_ERR_ARG: net or X NULL, P < 0, x_ld < 3.  P == 0 launches nothing. */
 int nu_sdf_jet_fwd(const NuSdfNet* net, const float* X, int x_ld, int P, float* sdf, float* grad, float* hess, float* mean,
                    float* gauss, float* normal, hipStream_t stream);
+/* Sphere tracing of the SDF as ONE fully-fused no-gradient kernel (csrc/sdf_trace.hip; network/tracing.py:103-164 called on each ray
+ * alone): persistent workgroups hold 64 ray slots in LDS, run the pipeline of nu_sdf_fused_fwd on the slot positions, apply the step
+ * behind the head and refill finished slots from a statically assigned ray sequence.  Per ray, every operation a separately rounded
+ * fp32 multiply / add / divide / square root in this order (f = the bits of nu_sdf_fused_fwd, Rb = bound_radius):
+ *   fgr = finite(o) && (fg == NULL || fg[r]);  x = o;  t = 0
+ *   if Rb > 0:  a = (d0 d0 + d1 d1) + d2 d2;  b = 2 ((d0 o0 + d1 o1) + d2 o2);  c = ((o0 o0 + o1 o1) + o2 o2) - Rb Rb
+ *               disc = b b - (4 a) c;  bounded = disc >= 0;  t0 = (-b - sqrt(disc)) / (2 a)
+ *               flags & NU_TRACE_ENTRY_FORWARD: t0 = max(t0, 0)   (off, the reference: an origin inside the sphere steps BACK to its entry)
+ *               if bounded: x = o + d t0, t = t0;   fgr &= bounded
+ *   for i < max_iter while fgr:  s = clamp(f(x), -10, 10), NaN -> 10;  x = x + d s;  t = t + s;  iters = i + 1;  sdf_last = s
+ *               if Rb > 0: fgr &= sqrt((x0 x0 + x1 x1) + x2 x2) < Rb;   conv = |s| < threshold;   stop when conv or !fgr
+ *   hit = conv && fgr;  pos, t = x, t as left.  A ray that never was foreground: pos = o, t = 0, iters = 0, sdf_last = 0, hit = 0.
+ *   O [R, o_ld], D [R, d_ld] (the first three floats of a row; leading dimensions >= 3), fg [R] bytes or NULL; pos [R,3], t [R],
+ *   sdf_last [R], iters [R] int, hit [R] bytes (0 / 1).  Every output pointer may be NULL.  No workspace, no host read.  A ray's result
+ *   does not depend on its neighbours, the ray order or the grid.  Reads the fp32 packed tables (every mlp_dtype has them).
+ *   NU_ERR_ARG: net, O or D NULL, R < 0, a leading dimension < 3, max_iter < 1, threshold not > 0.  R == 0 launches nothing. */
+#define NU_TRACE_ENTRY_FORWARD 1
+int nu_sdf_trace(const NuSdfNet* net, const float* O, int o_ld, const float* D, int d_ld, int R, const unsigned char* fg,
+                 int max_iter, float threshold, float bound_radius, int flags, float* pos, float* t, float* sdf_last, int* iters,
+                 unsigned char* hit, hipStream_t stream);
 int nu_sdf_mlp_normal(NuOpCtx* ctx, const NuSdfNet* net, NuSdfBufs* bufs, hipStream_t stream);
 int nu_sdf_mlp_bwd(NuOpCtx* ctx, const NuSdfNet* net, NuSdfBufs* bufs, const float* dYX, const float* nbar, float* dx,
                    hipStream_t stream);

@@ -19,6 +19,8 @@
 // head is one wave per row with the arithmetic of skinny_fwd_kernel<1, 256>.
 // Arithmetic order is that of the layered path (same MFMA, same k order, same softplus, same head reduction): BIT-identical
 // results, so the sampler's parity tests hold unchanged.
+// The pipeline of sdf_fused_fwd_kernel<2> below (weight cursor, MFMA schedule, epilogue, head) is repeated in sdf_jet.hip and sdf_trace.hip,
+// whose value rows must carry the bits of this kernel: a change here belongs there too (their tests compare against nu_sdf_fused_fwd).
 #include "gemm.h"
 
 #define FS_ALD 260                 // activation row stride (floats)

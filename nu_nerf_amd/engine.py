@@ -746,6 +746,18 @@ class Stage1Engine:
         self.lib.nu_sdf_jet_fwd(ctypes.byref(self._sdf_net), X, x_ld, P, addr(sdf), addr(grad), addr(hess), addr(mean), addr(gauss),
                                 addr(normal), self.stream())
 
+    # ------------------------------------------------------------------ SDF sphere tracing
+    def sdf_trace(self, O, o_ld, D, d_ld, R, *, fg=None, max_iter=200, threshold=1e-5, bound_radius=1.0, flags=0, pos=None, t=None,
+                  sdf=None, iters=None, hit=None):
+        """Sphere tracing of R rays (O, D: device addresses of [R, o_ld] / [R, d_ld] rows whose first 3 floats are origin / direction;
+        fg: uint8 [R] tensor or None) against the SDF network in ONE no-gradient kernel (csrc/sdf_trace.hip; the per-ray semantics are
+        stated at nu_sdf_trace in include/nu_nerf.h), written to the tensors given (pos [R,3], t, sdf [R] fp32; iters [R] int32; hit [R]
+        uint8; None: not written).  No workspace, no host read.  Reads the fp32 packed tables, which pack() writes in every mlp_dtype."""
+        if self._desc_dev is None or self._ptr_sig != self._signature():
+            self._upload_descs()
+        self.lib.nu_sdf_trace(ctypes.byref(self._sdf_net), O, o_ld, D, d_ld, R, addr(fg), max_iter, threshold, bound_radius, flags,
+                              addr(pos), addr(t), addr(sdf), addr(iters), addr(hit), self.stream())
+
     # ------------------------------------------------------------------ light bake
     def light_bake(self, dirs, kinv, N, x=None, x_stride=0, *, probe=False, light=None, direct=None, indirect=None, occ=None, enc=None,
                    raw=None):

@@ -344,6 +344,12 @@ class NeROShapeRenderer(nn.Module):
         from .environment import predict_environment
         return predict_environment(self, h, w, roughness, point, None, probe)
 
+    def render_surface(self, K, pose, h, w, **kw):
+        """Images of the SDF's surface from a pinhole camera (K [3,3], pose [3,4] world -> camera) without a mesh: 'mask', 'depth',
+        'normal', ... device tensors by one fused sphere-tracing kernel (sdf_trace.py)."""
+        from .sdf_trace import render_surface
+        return render_surface(self, K, pose, h, w, **kw)
+
     # ---- data ----------------------------------------------------------------------------------
     def _init_dataset(self):
         """Ray-batch store (renderer_zerothick.py:167-190).  `database_name: synthetic/<n_rays>` builds the seeded synthetic

@@ -224,6 +224,12 @@ class Stage2Renderer(nn.Module):
         from .environment import predict_environment
         return predict_environment(self, h, w, roughness, point, which, probe)
 
+    def render_surface(self, K, pose, h, w, which='inner', **kw):
+        """Images of an SDF's surface from a pinhole camera without a mesh (sdf_trace.py): which='inner' sdf_network_inner (materials:
+        color_network_inner), which='outer' the stage-1 networks."""
+        from .sdf_trace import render_surface
+        return render_surface(self, K, pose, h, w, which=which, **kw)
+
     def get_anneal_val(self, step):
         if self.cfg['anneal_end'] < 0:
             return 1.0
