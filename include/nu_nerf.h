@@ -400,6 +400,51 @@ int nu_relight_shadow_rays(const float* gbuf, const int* pix, int n_pix, int sam
 int nu_relight_env_lookup(const float* env, int env_h, int env_w, const float* dirs, int N, float* out, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Split-sum relighting from a prefiltered environment pyramid: the image formation the networks were trained
+ * under (network/field.py:684-735), evaluated on the baked mesh with no Monte-Carlo sum, no visibility and no interreflection.
+ *   nu_env_prefilter       zonal kernel regression on the sphere.  src_dir [M,4] = unit direction and quadrature weight w, src_rgb [M,4]
+ *                          (the fourth value is not read), dirs [N,3], L lobes (lobe_kind, lobe_param: HOST arrays [L]).
+ *                            out[l,i] = sum_j w_j f_l(c_ij) rgb_j / sum_j w_j f_l(c_ij),   c_ij = dirs_i . src_dir_j   (rgb; alpha = 1)
+ *                            NU_LOBE_COSINE      f = max(c, 0)                                       (param not read)
+ *                            NU_LOBE_GGX, alpha  f = c D(NoH) for c > 0, else 0;  NoH^2 = (1 + c) / 2,
+ *                                                D = alpha^2 / (pi (NoH^2 (alpha^2 - 1) + 1)^2)     (the GGX prefilter with N = V = R)
+ *                            NU_LOBE_VMF, kappa  f = exp(kappa (c - 1))
+ *                          out [L,N,4] is WRITTEN.  One query per thread, the source streamed through LDS, c shared by the lobes, sums
+ *                          in ONE fixed order (per tile of 256 source entries from zero, tiles added in order), no atomics: a
+ *                          query's bits do not depend on N, on its position or on the other lobes.  When N is too small to fill the
+ *                          chip the tile range is split over workgroups and folded in tile order by a second launch (the same
+ *                          additions, the same bits); that needs ws of nu_env_prefilter_workspace_bytes(N, M, L) bytes (a pure host
+ *                          function; 0 when the split is not taken; 16-byte aligned).
+ *                          NU_ERR_ARG: a NULL pointer (of an array that is not empty), N < 0, M < 0, L outside 1..NU_ENV_MAX_LOBES, an unknown kind, alpha <= 0,
+ *                          kappa <= 0 (or not finite).  NU_ERR_WORKSPACE: ws missing or too small.  N == 0 or M == 0 launches nothing.
+ *   nu_env_pyramid_lookup  out [N,3] = L(dirs_i, rho_i): pyr [L,ph,pw,4] RGBA fp32 (16-byte aligned), levels [L] a HOST array, strictly
+ *                          ascending, L <= NU_ENV_MAX_LOBES.  rho is clamped to [levels[0], levels[L-1]]; with levels[i] <= rho <=
+ *                          levels[i+1] (the largest such i), t = (rho - levels[i]) / (levels[i+1] - levels[i]) and the value is
+ *                          (1 - t) tap_i(d) + t tap_{i+1}(d), tap = the bilinear lat-long tap of nu_relight_env_lookup, its operations.
+ *                          L = 1: that level's tap.  At a level the value has the bits of that level's tap.
+ *   nu_relight_splitsum    the listed HIT pixels of a G-buffer (rows as above), out [rows of the G-buffer, 4] WRITTEN (rgb; alpha = 1):
+ *                            NoV = n.v;  r = 2 NoV n - v;  F0 = 0.04 (1 - m) + m a
+ *                            (A, B) = fg [256,256,2] bilinear at (clamp(NoV, 0, 1), clamp(rho, 0, 1)), texel centres at (i + 1/2) / 256,
+ *                                     clamped to the edge (the lookup of the training kernels)
+ *                            rgb = (1 - m) a Ld(n) + (F0 A + B) L(r, rho)
+ *                          Ld = diffuse [dh,dw,4], one bilinear tap; L = nu_env_pyramid_lookup's value.  Pixels that are not listed are
+ *                          not touched.
+ *                          NU_ERR_ARG (both): a NULL pointer, N / n_pix < 0, L outside 1..NU_ENV_MAX_LOBES, a map side <= 0, levels
+ *                          not finite or not strictly ascending.
+ * --------------------------------------------------------------------------------------------------------- */
+#define NU_ENV_MAX_LOBES 16
+#define NU_LOBE_COSINE 0
+#define NU_LOBE_GGX 1
+#define NU_LOBE_VMF 2
+long long nu_env_prefilter_workspace_bytes(int N, int M, int L);
+int nu_env_prefilter(const float* src_dir, const float* src_rgb, int M, const float* dirs, int N, const int* lobe_kind,
+                     const float* lobe_param, int L, float* out, void* ws, long long ws_bytes, hipStream_t stream);
+int nu_env_pyramid_lookup(const float* pyr, int L, int ph, int pw, const float* levels, const float* dirs, const float* rho, int N,
+                          float* out, hipStream_t stream);
+int nu_relight_splitsum(const float* gbuf, const int* pix, int n_pix, const float* pyr, int L, int ph, int pw, const float* levels,
+                        const float* diffuse, int dh, int dw, const float* fg, float* out, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Relighting of the NESTED object (the project's own transport, pinned against no other renderer): a
  * transparent outer shell (tree, V_o, F_o, unit vertex normals, index of refraction ior [V_o] >= 1) around an opaque inner mesh
  * (tree, V_i, F_i, unit vertex normals, materials_i [V_i,5]).  The outer G-buffer comes from nu_relight_gbuffer run on the outer mesh

@@ -162,3 +162,121 @@ extern "C" int nu_relight_env_lookup(const float* env, int env_h, int env_w, con
                        out);
     return nu_launch_status();
 }
+
+// ---- split-sum relighting from a prefiltered pyramid ---------------------------------------------------------------------
+struct RlLevels {                    // kernel argument: the ascending roughness levels of the pyramid
+    float v[NU_ENV_MAX_LOBES];
+};
+
+// L(d, rho) of the pyramid pyr [L, ph, pw] RGBA: rho clamped to the levels' range, the two levels around it tapped as nu_relight_env does
+// and mixed linearly.  At a level the weight of the other tap is exactly 0, so the value has the bits of that level's tap.
+static __device__ inline void nu_rl_pyramid(const float4* __restrict__ pyr, int L, int ph, int pw, const RlLevels& lv, const float* d,
+                                            float rho, float* rgb) {
+    if (L == 1) {
+        nu_relight_env(pyr, ph, pw, d, rgb);
+        return;
+    }
+    const float r = fminf(fmaxf(rho, lv.v[0]), lv.v[L - 1]);
+    int i = 0;
+    float lo = lv.v[0], hi = lv.v[1];
+#pragma unroll
+    for (int k = 1; k < NU_ENV_MAX_LOBES - 1; ++k)
+        if (k < L - 1 && r >= lv.v[k]) { i = k; lo = lv.v[k]; hi = lv.v[k + 1]; }
+    const float t = (r - lo) / (hi - lo);
+    float a[3], b[3];
+    const long long plane = (long long)ph * pw;
+    nu_relight_env(pyr + i * plane, ph, pw, d, a);
+    nu_relight_env(pyr + (i + 1) * plane, ph, pw, d, b);
+    for (int c = 0; c < 3; ++c) rgb[c] = (1.0f - t) * a[c] + t * b[c];
+}
+
+__global__ __launch_bounds__(256) void relight_pyramid_lookup_kernel(const float4* __restrict__ pyr, int L, int ph, int pw, RlLevels lv,
+                                                                     const float* __restrict__ dirs, const float* __restrict__ rho, int N,
+                                                                     float* __restrict__ out) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= N) return;
+    const float d[3] = {dirs[r * 3LL], dirs[r * 3LL + 1], dirs[r * 3LL + 2]};
+    float rgb[3];
+    nu_rl_pyramid(pyr, L, ph, pw, lv, d, rho[r], rgb);
+    for (int k = 0; k < 3; ++k) out[r * 3LL + k] = rgb[k];
+}
+
+// The levels of a call as a kernel argument; false when they are not finite and strictly ascending.
+static bool nu_rl_levels(const float* levels, int L, RlLevels& lv) {
+    for (int k = 0; k < NU_ENV_MAX_LOBES; ++k) lv.v[k] = 0.0f;
+    for (int k = 0; k < L; ++k) {
+        if (!(levels[k] > -3e38f && levels[k] < 3e38f) || (k > 0 && !(levels[k] > levels[k - 1]))) return false;
+        lv.v[k] = levels[k];
+    }
+    return true;
+}
+
+extern "C" int nu_env_pyramid_lookup(const float* pyr, int L, int ph, int pw, const float* levels, const float* dirs, const float* rho, int N,
+                                     float* out, hipStream_t stream) {
+    if (N < 0 || L < 1 || L > NU_ENV_MAX_LOBES || ph <= 0 || pw <= 0 || !pyr || !levels || (N > 0 && (!dirs || !rho || !out)))
+        return NU_ERR_ARG;
+    RlLevels lv;
+    if (!nu_rl_levels(levels, L, lv)) return NU_ERR_ARG;
+    if (N == 0) return NU_OK;
+    hipLaunchKernelGGL(relight_pyramid_lookup_kernel, dim3(nu_cdiv(N, 256)), dim3(256), 0, stream, (const float4*)pyr, L, ph, pw, lv, dirs,
+                       rho, N, out);
+    return nu_launch_status();
+}
+
+// (A, B) of the split-sum table fg [256,256,2] at (u, v) in [0,1]^2: the values of nu_lut (render.hip) -- texel centres at (i + 1/2) / 256,
+// bilinear, clamped to the edge -- restated without its derivatives.
+static __device__ inline void nu_rl_fg(const float* __restrict__ fg, float u, float v, float& A, float& B) {
+    const float fx = fminf(fmaxf(u * 256.0f - 0.5f, 0.f), 255.f), fy = fminf(fmaxf(v * 256.0f - 0.5f, 0.f), 255.f);
+    const int x0 = (int)floorf(fx), y0 = (int)floorf(fy);
+    const int x1 = x0 + 1 < 255 ? x0 + 1 : 255, y1 = y0 + 1 < 255 ? y0 + 1 : 255;
+    const float tx = fx - (float)x0, ty = fy - (float)y0;
+    const float2 l00 = *(const float2*)(fg + (y0 * 256 + x0) * 2), l01 = *(const float2*)(fg + (y0 * 256 + x1) * 2);
+    const float2 l10 = *(const float2*)(fg + (y1 * 256 + x0) * 2), l11 = *(const float2*)(fg + (y1 * 256 + x1) * 2);
+    A = (l00.x * (1 - tx) + l01.x * tx) * (1 - ty) + (l10.x * (1 - tx) + l11.x * tx) * ty;
+    B = (l00.y * (1 - tx) + l01.y * tx) * (1 - ty) + (l10.y * (1 - tx) + l11.y * tx) * ty;
+}
+
+// One thread per listed hit pixel: rgb = (1 - m) a Ld(n) + (F0 A + B) L(reflect(v, n), rho), written.
+__global__ __launch_bounds__(256) void relight_splitsum_kernel(const float* __restrict__ gbuf, const int* __restrict__ pix, int n_pix,
+                                                               const float4* __restrict__ pyr, int L, int ph, int pw, RlLevels lv,
+                                                               const float4* __restrict__ diffuse, int dh, int dw,
+                                                               const float* __restrict__ fg, float* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pix) return;
+    const long long row = pix[i];
+    float g[NU_RL_ROW];
+#pragma unroll
+    for (int k = 0; k < NU_RL_ROW; k += 4) {
+        const float4 q = *(const float4*)(gbuf + row * NU_RL_ROW + k);
+        g[k] = q.x; g[k + 1] = q.y; g[k + 2] = q.z; g[k + 3] = q.w;
+    }
+    const float* n = g + 7;
+    const float* v = g + 15;
+    const float m = g[13], rho = g[14];
+    const float nov = nu_rl_dot3(n, v);
+    float r[3], ld[3], ls[3], A, B;
+    for (int c = 0; c < 3; ++c) r[c] = (2.0f * nov) * n[c] - v[c];
+    nu_relight_env(diffuse, dh, dw, n, ld);
+    nu_rl_pyramid(pyr, L, ph, pw, lv, r, rho, ls);
+    nu_rl_fg(fg, fminf(fmaxf(nov, 0.f), 1.f), fminf(fmaxf(rho, 0.f), 1.f), A, B);
+    float4 o;
+    float rgb[3];
+    for (int c = 0; c < 3; ++c) {
+        const float f0 = 0.04f * (1.0f - m) + m * g[10 + c];
+        rgb[c] = ((1.0f - m) * g[10 + c]) * ld[c] + (f0 * A + B) * ls[c];
+    }
+    o.x = rgb[0]; o.y = rgb[1]; o.z = rgb[2]; o.w = 1.0f;
+    *(float4*)(out + row * 4) = o;
+}
+
+extern "C" int nu_relight_splitsum(const float* gbuf, const int* pix, int n_pix, const float* pyr, int L, int ph, int pw, const float* levels,
+                                   const float* diffuse, int dh, int dw, const float* fg, float* out, hipStream_t stream) {
+    if (n_pix < 0 || L < 1 || L > NU_ENV_MAX_LOBES || ph <= 0 || pw <= 0 || dh <= 0 || dw <= 0) return NU_ERR_ARG;
+    if (!gbuf || (n_pix > 0 && !pix) || !pyr || !levels || !diffuse || !fg || !out) return NU_ERR_ARG;      // an empty hit list may have no address
+    RlLevels lv;
+    if (!nu_rl_levels(levels, L, lv)) return NU_ERR_ARG;
+    if (n_pix == 0) return NU_OK;
+    hipLaunchKernelGGL(relight_splitsum_kernel, dim3(nu_cdiv(n_pix, 256)), dim3(256), 0, stream, gbuf, pix, n_pix, (const float4*)pyr, L, ph,
+                       pw, lv, (const float4*)diffuse, dh, dw, fg, out);
+    return nu_launch_status();
+}

@@ -160,3 +160,161 @@ def write_hdr(path, img):
 def predict_environment(renderer, h=256, w=512, roughness=0.0, point=None, which=None, probe=False):
     """What the renderer classes' predict_environment returns: environment_map."""
     return environment_map(renderer, h, w, roughness, point, which, probe)
+
+
+# ---- prefiltering into the roughness pyramid of the split-sum model (DESIGN.md 28) ----------------------------------------------------
+LOBE_KINDS = {'cosine': L.NU_LOBE_COSINE, 'ggx': L.NU_LOBE_GGX, 'vmf': L.NU_LOBE_VMF}
+ALPHA_MIN = 1e-3                # NU_RL_ALPHA_MIN of csrc/relight.h
+DEFAULT_LEVELS = (0.0, 0.25, 0.5, 0.75, 1.0)
+
+
+def _pf_bad(what, why):
+    return L.NuNerfLibraryError(f"nu_env_prefilter failed with code -1 (NU_ERR_ARG): {what} {why}")
+
+
+def lobe_param(kind, roughness):
+    """The kernel's parameter of a lobe given by the roughness it serves: GGX alpha = max(rho^2, ALPHA_MIN); vMF kappa = 1 / rho (the
+    kappa_inv of the integrated directional encoding); the cosine lobe has none (0)."""
+    if kind not in LOBE_KINDS:
+        raise ValueError(f"lobe kind must be one of {sorted(LOBE_KINDS)}, got {kind!r}")
+    if kind == 'cosine':
+        return 0.0
+    rho = float(roughness)
+    if kind == 'ggx':
+        return max(rho * rho, ALPHA_MIN)
+    if not rho > 0.0:
+        raise ValueError(f"a vMF lobe needs a roughness > 0, got {roughness}")
+    return 1.0 / rho
+
+
+def lobe_falloff(kind, roughness, angle):
+    """f(cos angle) / f(1) of the lobe in float64: its weight `angle` radians off axis relative to its peak."""
+    c = np.cos(np.float64(angle))
+    p = np.float64(lobe_param(kind, roughness))
+    if kind == 'cosine':
+        return max(c, 0.0)
+    if kind == 'ggx':
+        a2 = p * p
+        return max(c, 0.0) * (a2 / (a2 + (1.0 - a2) * (1.0 - c) * 0.5)) ** 2
+    return float(np.exp(p * (c - 1.0)))
+
+
+def lobe_is_tapped(kind, roughness, src_height):
+    """The tap rule: a level whose lobe is narrower than the source grid is served by the bilinear tap of the source instead of the
+    regression -- its weight one source pitch (pi / src_height) off axis is below half its peak.  Roughness 0 always is (a sub-texel
+    lobe over a texel-box map is the texel); the cosine lobe never is."""
+    if kind == 'cosine':
+        return False
+    if float(roughness) <= 0.0:
+        return True
+    return bool(lobe_falloff(kind, roughness, np.pi / int(src_height)) < 0.5)
+
+
+def source_table(env):
+    """(src_dir [H*W,4], src_rgb [H*W,4]) float32 numpy of a lat-long map [H,W,3]: latlong_dirs' texel-centre directions with the
+    quadrature weight w = sin theta (float64, then rounded; > 0 at every texel centre, the poles included), and the texels."""
+    env = np.asarray(env)
+    if env.ndim != 3 or env.shape[2] != 3 or env.shape[0] < 1 or env.shape[1] < 1:
+        raise ValueError(f"environment map must be [H,W,3], got {env.shape}")
+    if not np.isfinite(env).all():
+        raise ValueError("environment map has non-finite values")
+    h, w = env.shape[:2]
+    theta = (np.arange(h, dtype=np.float64) + 0.5) * np.pi / h
+    sd = np.empty((h * w, 4), np.float32)
+    sd[:, :3] = latlong_dirs(h, w)
+    sd[:, 3] = np.repeat(np.sin(theta), w)
+    rgb = np.zeros((h * w, 4), np.float32)
+    rgb[:, :3] = env.reshape(h * w, 3)
+    return sd, rgb
+
+
+def _lobes(lobes):
+    out = []
+    for item in lobes:
+        kind, rho = (item, None) if isinstance(item, str) else item
+        out.append((LOBE_KINDS[kind] if kind in LOBE_KINDS else -1, lobe_param(kind, rho)))
+    if not 1 <= len(out) <= L.NU_ENV_MAX_LOBES:
+        raise _pf_bad("lobes", f"must number 1..{L.NU_ENV_MAX_LOBES}, got {len(out)}")
+    return out
+
+
+def _pf_rows(t, dev, what, cols):
+    if not torch.is_tensor(t):
+        t = torch.as_tensor(np.ascontiguousarray(t, dtype=np.float32)).to(dev)
+    if not t.is_cuda:
+        raise _pf_bad(what, "are not on the GPU")
+    if t.dtype != torch.float32:
+        raise _pf_bad(what, f"have dtype {t.dtype}, expected float32")
+    if t.dim() != 2 or t.shape[1] != cols:
+        raise _pf_bad(what, f"have shape {tuple(t.shape)}, expected [N, {cols}]")
+    if not t.is_contiguous():
+        raise _pf_bad(what, "are not contiguous")
+    return t
+
+
+@torch.no_grad()
+def prefilter_dirs(env, dirs, lobes, device=None):
+    """The raw entry (one nu_env_prefilter call): out [L,N,4] float32 on the device, rgb = the lobe-weighted mean of the source around each
+    direction, alpha = 1.  env: a lat-long map [H,W,3] (source_table makes the point set) or a weighted point set (src_dir [M,4] = unit
+    direction and weight, src_rgb [M,4]); dirs [N,3]; lobes: a sequence of 'cosine', ('ggx', roughness) or ('vmf', roughness), at most
+    NU_ENV_MAX_LOBES.  Arrays are taken to the device; tensors must be float32, contiguous and on it.  A query's bits do not depend on
+    the other queries or lobes of the call."""
+    import ctypes
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    if isinstance(env, (tuple, list)):
+        sd, rgb = env
+    else:
+        sd, rgb = source_table(env.cpu().numpy() if torch.is_tensor(env) else env)
+    sd, rgb, dirs = _pf_rows(sd, dev, "source directions", 4), _pf_rows(rgb, dev, "source values", 4), _pf_rows(dirs, dev, "dirs", 3)
+    if rgb.shape[0] != sd.shape[0]:
+        raise _pf_bad("source values", f"have shape {tuple(rgb.shape)}, expected [{sd.shape[0]}, 4]")
+    table = _lobes(lobes)
+    nl, N, M = len(table), int(dirs.shape[0]), int(sd.shape[0])
+    out = torch.empty(nl, N, 4, dtype=torch.float32, device=dev)
+    lib = L.load()
+    need = lib.nu_env_prefilter_workspace_bytes(N, M, nl)
+    ws = torch.empty(need // 4, dtype=torch.float32, device=dev) if need else None
+    kinds = (ctypes.c_int * nl)(*[k for k, _ in table])
+    params = (ctypes.c_float * nl)(*[p for _, p in table])
+    lib.nu_env_prefilter(L.ptr(sd), L.ptr(rgb), M, L.ptr(dirs), N, kinds, params, nl, L.ptr(out), L.ptr(ws), need, L.stream())
+    return out
+
+
+@torch.no_grad()
+def prefilter(env, roughness=DEFAULT_LEVELS, height=None, width=None, lobe='ggx', diffuse='cosine', device=None):
+    """A lat-long map [H,W,3] prefiltered into the split-sum pyramid -> (pyramid [L,h,w,3], diffuse [h,w,3], info), float32 numpy in
+    latlong_dirs' convention (h, w default to the source's).  Level l is the `lobe` ('ggx' or 'vmf') of roughness[l]; the diffuse map is
+    the 'cosine' lobe (irradiance / pi) or, with diffuse='vmf', the vMF lobe of roughness 1 (the integrated directional encoding's own
+    convention, as lobe='vmf').  Levels under the tap rule (lobe_is_tapped) are the bilinear tap of the source (relight.env_lookup);
+    every other level and the diffuse map come from ONE nu_env_prefilter call.  info: 'tapped' (the indices of the tapped levels),
+    'lobes' (what the call evaluated), 'pairs' (queries x source points x lobes of the call).  The work is that product: it grows with the
+    square of the map's area when h, w follow the source (28 ms for 256 x 512 on an MI355X); a smaller query grid is enough
+    for the rough levels of a large map."""
+    from .relight import env_lookup, pack_env
+    if lobe not in ('ggx', 'vmf') or diffuse not in ('cosine', 'vmf'):
+        raise ValueError(f"lobe must be 'ggx' or 'vmf' and diffuse 'cosine' or 'vmf', got {lobe!r}, {diffuse!r}")
+    env = np.ascontiguousarray(env.cpu().numpy() if torch.is_tensor(env) else env, dtype=np.float32)
+    levels = [float(r) for r in np.atleast_1d(np.asarray(roughness, dtype=np.float64))]
+    if not levels or any(r < 0.0 for r in levels):
+        raise ValueError(f"roughness levels must be >= 0 and at least one, got {roughness}")
+    sd, rgb = source_table(env)
+    H, W = env.shape[:2]
+    h, w = int(height or H), int(width or W)
+    dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+    dirs = torch.from_numpy(latlong_dirs(h, w)).to(dev)
+    tapped = [i for i, r in enumerate(levels) if lobe_is_tapped(lobe, r, H)]
+    lobes = [(lobe, r) for i, r in enumerate(levels) if i not in tapped] + ['cosine' if diffuse == 'cosine' else ('vmf', 1.0)]
+    reg = prefilter_dirs((sd, rgb), dirs, lobes, dev)[..., :3].cpu().numpy().reshape(len(lobes), h, w, 3)
+    pyramid = np.empty((len(levels), h, w, 3), np.float32)
+    if tapped:
+        tap = env_lookup(torch.from_numpy(pack_env(env)).to(dev), dirs).cpu().numpy().reshape(h, w, 3)
+    k = 0
+    for i in range(len(levels)):
+        if i in tapped:
+            pyramid[i] = tap
+        else:
+            pyramid[i] = reg[k]
+            k += 1
+    info = {'tapped': tapped, 'lobes': [x if isinstance(x, str) else [x[0], x[1]] for x in lobes], 'pairs': h * w * H * W * len(lobes),
+            'source': [H, W], 'shape': [len(levels), h, w, 3]}
+    return pyramid, np.ascontiguousarray(reg[-1]), info

@@ -1,5 +1,5 @@
 """python -m nu_nerf_amd.relight --mesh PLY --material DIR --hdr FILE --name NAME [--trans] [--num 360 --width 800 --height 800
---samples 1024 --cam_dist 3.0 --azimuth 0 --elevation 45] [--inner PLY --inner-material DIR (--ior VALUE_OR_DIR | --shell DIR_OR_PAIR [--shell-curvature FILE])]
+--samples 1024 --cam_dist 3.0 --azimuth 0 --elevation 45] [--splitsum [--pyramid DIR | --levels R ...]] [--inner PLY --inner-material DIR (--ior VALUE_OR_DIR | --shell DIR_OR_PAIR [--shell-curvature FILE])]
 
 relight.py + blender_backend/relight_backend.py on the GPU: the extracted mesh, the per-vertex DIR/metallic.npy, roughness.npy and
 albedo.npy that extract_materials writes and a lat-long HDR environment map are rendered from the reference's camera orbit
@@ -19,6 +19,12 @@ extract_materials --stage2 wrote for such a config, or "IOR,THICKNESS" (two numb
 --hdr takes a Radiance .hdr (RGBE, flat or run-length scanlines) or a .npy float [H,W,3]; the map is z up in the mesh's frame.
 --focal_mm / --sensor_mm: Blender's default camera (50 mm on a 36 mm sensor fitted to the larger image side).  --seed, --chunk
 (samples per pass; bounds device memory) and --output (default data/relight/NAME) are this project's own.
+
+--splitsum: the deterministic second path, the split-sum image formation the networks were trained under evaluated from a
+prefiltered roughness pyramid -- no sampling, no noise, no shadows: a frame is its G-buffer pass and one resolve launch.  With --hdr the
+map is prefiltered at --levels (default 0 .25 .5 .75 1; environment.prefilter); with --pyramid DIR it reads env_pyramid.npy,
+roughness.npy and, if present, env_diffuse.npy (otherwise the diffuse map is the level of roughness 1), so a directory written by
+extract_environment or prefilter_environment works as it is.  --samples, --seed and --chunk are not used; --inner is refused.
 """
 import argparse
 import os
@@ -305,6 +311,127 @@ def relight(V, F, materials, env, poses, h, w, samples, seed=0, chunk=256, **kw)
     return to_srgb8(relight_linear(V, F, materials, env, poses, h, w, samples, seed, chunk, **kw))
 
 
+# ---- split-sum relighting from a prefiltered pyramid ------------------------------------------------------------------
+MAX_LEVELS = 16                 # NU_ENV_MAX_LOBES
+_FG = {}
+
+
+def fg_table(device):
+    """The split-sum table (params.load_fg_lut) [256,256,2] on the device, uploaded once per device."""
+    import torch
+    from .params import load_fg_lut
+    key = str(device)
+    if key not in _FG:
+        _FG[key] = torch.from_numpy(np.ascontiguousarray(load_fg_lut().reshape(256, 256, 2))).to(device)
+    return _FG[key]
+
+
+def pack_pyramid(pyramid, levels):
+    """(float32 [L,h,w,4] RGBA, float32 [L]) from a pyramid [L,h,w,3] and its roughness levels: finite, strictly ascending, at most
+    MAX_LEVELS."""
+    pyramid, levels = np.asarray(pyramid, np.float32), np.asarray(levels, np.float32).reshape(-1)
+    if pyramid.ndim != 4 or pyramid.shape[3] != 3 or min(pyramid.shape) < 1:
+        raise ValueError(f"pyramid must be [L,h,w,3], got {pyramid.shape}")
+    if levels.shape[0] != pyramid.shape[0] or not 1 <= levels.shape[0] <= MAX_LEVELS:
+        raise ValueError(f"levels must give one roughness for each of the 1..{MAX_LEVELS} pyramid levels, got {levels.shape} for {pyramid.shape}")
+    if not np.isfinite(levels).all() or (np.diff(levels) <= 0).any():
+        raise ValueError(f"levels must be finite and strictly ascending, got {levels.tolist()}")
+    if not np.isfinite(pyramid).all():
+        raise ValueError("pyramid has non-finite values")
+    return np.ascontiguousarray(np.concatenate([pyramid, np.ones_like(pyramid[..., :1])], -1)), np.ascontiguousarray(levels)
+
+
+def _levels_arg(levels):
+    import ctypes
+    levels = np.asarray(levels, np.float32).reshape(-1)
+    return (ctypes.c_float * len(levels))(*levels.tolist()), len(levels)
+
+
+def pyramid_lookup(pyr, levels, dirs, rho):
+    """L(d, rho) [N,3] of the packed pyramid pyr [L,h,w,4] (device) with roughness `levels` [L] (host) at dirs [N,3], rho [N]: rho clamped
+    to the levels' range, the two levels around it tapped as env_lookup does and mixed linearly."""
+    import torch
+    from . import _lib as L
+    for t, shape, what in ((pyr, (None, None, None, 4), 'pyramid'), (dirs, (None, 3), 'dirs'), (rho, (dirs.shape[0],), 'rho')):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != len(shape) \
+                or any(s is not None and int(d) != int(s) for d, s in zip(t.shape, shape)):
+            raise L.NuNerfLibraryError(f"nu_env_pyramid_lookup failed with code -1 (NU_ERR_ARG): {what} must be a contiguous float32 "
+                                       f"device tensor of shape {list(shape)}")
+    lv, nl = _levels_arg(levels)
+    if nl != pyr.shape[0]:
+        raise L.NuNerfLibraryError(f"nu_env_pyramid_lookup failed with code -1 (NU_ERR_ARG): {nl} levels for a pyramid of {pyr.shape[0]}")
+    out = torch.empty(dirs.shape[0], 3, dtype=torch.float32, device=dirs.device)
+    L.load().nu_env_pyramid_lookup(L.ptr(pyr), nl, int(pyr.shape[1]), int(pyr.shape[2]), lv, L.ptr(dirs), L.ptr(rho), int(dirs.shape[0]),
+                                   L.ptr(out), L.stream())
+    return out
+
+
+def splitsum_resolve(gbuf, pix, pyr, levels, diffuse, out):
+    """out [rows of gbuf, 4] = the split-sum colour of the listed hit pixels (pyr [L,h,w,4], diffuse [dh,dw,4]: packed, on the device)."""
+    from . import _lib as L
+    lv, nl = _levels_arg(levels)
+    L.load().nu_relight_splitsum(L.ptr(gbuf), L.ptr(pix), int(pix.shape[0]), L.ptr(pyr), nl, int(pyr.shape[1]), int(pyr.shape[2]), lv,
+                                 L.ptr(diffuse), int(diffuse.shape[0]), int(diffuse.shape[1]), L.ptr(fg_table(gbuf.device)), L.ptr(out),
+                                 L.stream())
+    return out
+
+
+def relight_splitsum_linear(V, F, materials, pyramid, levels, diffuse, poses, h, w, rows=None, images=1, K=None):
+    """Linear radiance float32 [n,h,w,4] (alpha 1 on hit pixels, 0 elsewhere) of the split-sum model the networks were trained under:
+    (1 - metallic) albedo Ld(n) + (F0 A + B) L(reflect(v, n), roughness), L from the prefiltered `pyramid` [L,ph,pw,3] at the roughness
+    `levels` [L], Ld from `diffuse` [dh,dw,3], (A, B) from the shipped table.  No sampling, no visibility, no interreflection: a frame is
+    its G-buffer pass and one resolve launch.  The Scene, cameras, G-buffer and hit list are relight_linear's; the result does not depend
+    on `rows` / `images`, bit for bit."""
+    import torch
+    from .mask_render import _cams
+    if images < 1 or (rows is not None and rows < 1):
+        raise ValueError("rows and images must be >= 1")
+    scene = _scene(V, F, materials)
+    dev = scene.device
+    pyr, lv = pack_pyramid(pyramid, levels)
+    pyr, dif = torch.from_numpy(pyr).to(dev), torch.from_numpy(pack_env(diffuse)).to(dev)
+    poses = np.asarray(poses.cpu() if torch.is_tensor(poses) else poses, np.float64).reshape(-1, 3, 4)
+    K = intrinsics(h, w) if K is None else np.asarray(K, np.float64)
+    cams = _cams(K.astype(np.float32), poses.astype(np.float32), dev)
+    n, rows = int(cams.shape[0]), int(rows or h)
+    out = torch.zeros(n, h, w, 4, dtype=torch.float32, device=dev)
+    for i0 in range(0, n, images):
+        ni = min(images, n - i0)
+        for y0 in range(0, h, rows):
+            nr = min(rows, h - y0)
+            face, gbuf = gbuffer(scene, cams[i0:i0 + ni], h, w, i0, y0, nr)
+            piece = torch.zeros(ni * nr * w, 4, dtype=torch.float32, device=dev)
+            splitsum_resolve(gbuf, hit_pixels(face), pyr, lv, dif, piece)
+            out[i0:i0 + ni, y0:y0 + nr] = piece.reshape(ni, nr, w, 4)
+    return out
+
+
+def relight_splitsum(V, F, materials, pyramid, levels, diffuse, poses, h, w, **kw):
+    """uint8 [n,h,w,4] sRGB + alpha of relight_splitsum_linear (same arguments)."""
+    return to_srgb8(relight_splitsum_linear(V, F, materials, pyramid, levels, diffuse, poses, h, w, **kw))
+
+
+def load_pyramid_dir(directory):
+    """(pyramid [L,h,w,3], levels [L], diffuse [dh,dw,3]) of a directory as extract_environment or prefilter_environment writes it:
+    env_pyramid.npy, roughness.npy and, if present, env_diffuse.npy.  Without env_diffuse.npy the diffuse map is the level whose
+    roughness is 1 (what the model's diffuse light queries); no such level is an error."""
+    pyramid = np.load(os.path.join(directory, 'env_pyramid.npy'))
+    levels = np.load(os.path.join(directory, 'roughness.npy')).reshape(-1)
+    if pyramid.ndim != 4 or pyramid.shape[3] != 3 or pyramid.shape[0] != levels.shape[0]:
+        raise ValueError(f"{directory}: env_pyramid.npy {pyramid.shape} and roughness.npy {levels.shape} are not [L,h,w,3] and [L]")
+    path = os.path.join(directory, 'env_diffuse.npy')
+    if os.path.exists(path):
+        diffuse = np.load(path)
+    else:
+        one = np.flatnonzero(levels == 1.0)
+        if one.size == 0:
+            raise ValueError(f"{directory}: no env_diffuse.npy and no pyramid level of roughness 1 (levels {levels.tolist()}) to take the "
+                             "diffuse map from")
+        diffuse = pyramid[int(one[0])]
+    order = np.argsort(levels, kind='stable')
+    return np.ascontiguousarray(pyramid[order], np.float32), np.ascontiguousarray(levels[order], np.float32), np.asarray(diffuse, np.float32)
+
+
 # ---- the nested object (DESIGN.md 21) ------------------------------------------------------------------------------------------------
 MAX_SEGMENTS = 4                # NU_RLN_MAX_SEGMENTS: interior segments of a camera path before the pixel counts as dark
 CHAIN = 12                      # floats per chain record (include/nu_nerf.h)
@@ -555,7 +682,13 @@ def parse_args(argv=None):
     # --inner-material, which argparse refuses as ambiguous; abbreviations stay allowed, as the command without --inner always had them
     nested = any(a == '--inner' or a.startswith('--inner=') for a in args)
     ap.add_argument('--material', type=str, required=not nested, help="directory with metallic.npy, roughness.npy, albedo.npy")
-    ap.add_argument('--hdr', type=str, required=True, help="environment map: Radiance .hdr or .npy float [H,W,3]")
+    splitsum = any(a == '--splitsum' for a in args)
+    ap.add_argument('--hdr', type=str, required=not splitsum, help="environment map: Radiance .hdr or .npy float [H,W,3]")
+    ap.add_argument('--splitsum', action='store_true', default=False,
+                    help="deterministic split-sum relighting from a prefiltered pyramid (no sampling, no shadows) instead of the Monte-Carlo path")
+    ap.add_argument('--pyramid', type=str, default=None,
+                    help="with --splitsum: a directory with env_pyramid.npy and roughness.npy (extract_environment, prefilter_environment) instead of --hdr")
+    ap.add_argument('--levels', type=float, nargs='+', default=None, help="with --splitsum --hdr: roughness levels of the pyramid (default 0 .25 .5 .75 1)")
     ap.add_argument('--name', type=str, required=True, help="frames go to data/relight/NAME")
     ap.add_argument('--trans', action='store_true', default=False, help="turn the mesh +90 degrees about x")
     ap.add_argument('--inner', type=str, default=None, help="inner mesh (PLY): --mesh is then the transparent shell around it")
@@ -583,6 +716,16 @@ def parse_args(argv=None):
         ap.error("--samples must be even and >= 2")
     if flags.num < 1 or flags.width < 1 or flags.height < 1 or flags.chunk < 1:
         ap.error("--num, --width, --height and --chunk must be >= 1")
+    if not flags.splitsum and (flags.pyramid is not None or flags.levels is not None):
+        ap.error("--pyramid and --levels need --splitsum")
+    if flags.splitsum:
+        if flags.inner is not None:
+            ap.error("--splitsum renders the plain object only: nested and thin-shell scenes (--inner) keep the Monte-Carlo path")
+        if (flags.hdr is None) == (flags.pyramid is None):
+            ap.error("--splitsum takes exactly one of --hdr and --pyramid")
+        if flags.levels is not None and (flags.pyramid is not None or any(r < 0.0 for r in flags.levels)
+                                         or sorted(set(flags.levels)) != flags.levels or len(flags.levels) > MAX_LEVELS):
+            ap.error(f"--levels needs --hdr and at most {MAX_LEVELS} ascending roughness values >= 0")
     if flags.shell is not None and flags.ior is not None:
         ap.error("--shell and --ior exclude each other: the shell is either the thin wall or solid glass")
     if flags.shell_curvature is not None and flags.shell is None:
@@ -698,11 +841,22 @@ def main(argv=None):
             scene = ThinShellScene(V, F, ior, thickness, Vi, Fi, load_materials(flags.inner_material), curvature=curvature)
         else:
             scene = NestedScene(V, F, load_ior(parse_ior(flags.ior), len(V)), Vi, Fi, load_materials(flags.inner_material))
-    env = read_hdr(flags.hdr)
+    if flags.splitsum:
+        print('--splitsum: --samples, --seed and --chunk are not used (nothing is sampled)')
+        if flags.pyramid is not None:
+            pyramid, levels, diffuse = load_pyramid_dir(flags.pyramid)
+        else:
+            from .environment import DEFAULT_LEVELS, prefilter
+            levels = np.asarray(flags.levels or DEFAULT_LEVELS, np.float32)
+            pyramid, diffuse, _ = prefilter(read_hdr(flags.hdr), levels)
+    else:
+        env = read_hdr(flags.hdr)
     poses = camera_in_mesh_frame(relighting_poses(flags.num, flags.azimuth, flags.elevation, flags.cam_dist))
     K = intrinsics(flags.height, flags.width, flags.focal_mm, flags.sensor_mm)
     for k in todo:
-        if flags.inner is None:
+        if flags.splitsum:
+            img = relight_splitsum(scene, None, None, pyramid, levels, diffuse, poses[k:k + 1], flags.height, flags.width, K=K)
+        elif flags.inner is None:
             img = relight(scene, None, None, env, poses[k:k + 1], flags.height, flags.width, flags.samples, flags.seed, flags.chunk, K=K, img0=k)
         else:
             img = relight_nested(scene, env, poses[k:k + 1], flags.height, flags.width, flags.samples, flags.seed, flags.chunk, K=K, img0=k)
