@@ -445,6 +445,55 @@ int nu_relight_splitsum(const float* gbuf, const int* pix, int n_pix, const floa
                         const float* diffuse, int dh, int dw, const float* fg, float* out, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Visibility transfer and shadowed split-sum relighting (the project's own quantity, the reference has no
+ * counterpart).  All launches on `stream`, no allocation, no atomics, no workspace.
+ *   nu_transfer_bake       per surface point i of points [n,3] with UNIT normals [n,3] (a precondition), hashed as id0 + i: `samples`
+ *                          (>= 16, a multiple of 16) cosine-weighted hemisphere rays about the normal, origin p + eps n, made in
+ *                          registers and traced any-hit against the tree of nu_lbvh_build with tmin = 0, tmax = radius (> 0; 1e16 =
+ *                          unbounded, as every other trace).  Sample j of S: Hammersley point (floor(j 2^32 / S), bitreverse32(j)) shifted
+ *                          (modulo 2^32) by two hash words of (id, seed), uniforms = the top 24 bits x 2^-24, cos = sqrt(1 - u2),
+ *                          sin = sqrt(u2), phi = 2 pi u1 in the orthonormal frame of the normal.  out [n,16] is WRITTEN, V_s = 1 where
+ *                          ray s meets nothing:
+ *                            [0..8]   T_k = (1/S) sum_s V_s Y_k(w_s): order-2 real SH in the order (0,0) (1,-1) (1,0) (1,1) (2,-2) .. (2,2),
+ *                                     0.282095; 0.488603 (y, z, x); 1.092548 xy, 1.092548 yz, 0.315392 (3 z^2 - 1), 1.092548 xz,
+ *                                     0.546274 (x^2 - y^2) -- an estimate of the integral of V (cos / pi) Y_k
+ *                            [9]      ambient occlusion = (float)(unoccluded samples) / (float)S
+ *                            [10..12] bent normal normalize(sum_s V_s w_s); the input normal when the sum is shorter than 1e-12
+ *                            [13..15] 0
+ *                          One single-wave block per point, 16 samples per round, summed in sample order in fp32: a row's bits depend on
+ *                          (point, normal, id, samples, seed, eps, radius, mesh) only -- not on n, the row's position or its neighbours.
+ *   nu_transfer_bake_dump  the same kernel; also vis [n,samples] uint8 = V_s (tests)
+ *   nu_transfer_rays       the rays nu_transfer_bake traces, rays [n * samples, 6]; bits (may be NULL) [n * samples, 2] = the two 24-bit
+ *                          sample integers (tests; not on the hot path)
+ *                          NU_ERR_ARG (all three): a NULL pointer of an array that is not empty, n < 0, n_faces <= 0, samples < 16 or not
+ *                          a multiple of 16, eps or radius not finite, radius <= 0, n * samples >= 2^31 (the caller chunks over points).
+ *                          n == 0 launches nothing.
+ *   nu_relight_splitsum_occluded   nu_relight_splitsum shadowed by a transfer [Nv,16] of the mesh's vertices.  face = the G-buffer pass's
+ *                          face ids, V, F = the mesh.  With x the stored hit point of a listed pixel and (v0, v1, v2) its face:
+ *                            e1 = v1 - v0, e2 = v2 - v0, t = x - v0, den = (e1.e1)(e2.e2) - (e1.e2)^2,
+ *                            u = ((e2.e2)(t.e1) - (e1.e2)(t.e2)) / den, v = ((e1.e1)(t.e2) - (e1.e2)(t.e1)) / den  (u = v = 0 unless den > 0)
+ *                            row = r0 + u (r1 - r0) + v (r2 - r0) over columns 0..12, the bent normal renormalised
+ *                            so = clamp(pow(clamp(NoV, 0, 1) + ao, exp2(-16 rho - 1)) - 1 + ao, 0, 1)       (Lagarde & de Rousiers 2014)
+ *                          and D = (1 - m) a Ld(n), Sp = (F0 A + B) L(r, rho) the two terms of nu_relight_splitsum (its operations):
+ *                            NU_OCC_AO   rgb = ao D + so Sp           -- the bits of nu_relight_splitsum where ao = 1
+ *                            NU_OCC_SH   rgb = (1 - m) a max(sum_k T_k L_k, 0) + so Sp,   L_k = envsh [9,4] row k (RGB + pad, 16-byte
+ *                                        aligned): the order-2 SH coefficients of the environment (not read in NU_OCC_AO)
+ *                          NU_ERR_ARG: as nu_relight_splitsum, a NULL face / V / F / transfer, an unknown mode.
+ * --------------------------------------------------------------------------------------------------------- */
+#define NU_OCC_AO 0
+#define NU_OCC_SH 1
+int nu_transfer_bake(const void* bvh, int n_faces, const float* points, const float* normals, int n, int id0, int samples, int seed,
+                     float eps, float radius, float* out, hipStream_t stream);
+int nu_transfer_bake_dump(const void* bvh, int n_faces, const float* points, const float* normals, int n, int id0, int samples, int seed,
+                          float eps, float radius, float* out, unsigned char* vis, hipStream_t stream);
+int nu_transfer_rays(const float* points, const float* normals, int n, int id0, int samples, int seed, float eps, float* rays, int* bits,
+                     hipStream_t stream);
+int nu_relight_splitsum_occluded(const float* gbuf, const int* face, const int* pix, int n_pix, const float* V, const int* F,
+                                 const float* transfer, const float* envsh, int mode, const float* pyr, int L, int ph, int pw,
+                                 const float* levels, const float* diffuse, int dh, int dw, const float* fg, float* out,
+                                 hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Relighting of the NESTED object (the project's own transport, pinned against no other renderer): a
  * transparent outer shell (tree, V_o, F_o, unit vertex normals, index of refraction ior [V_o] >= 1) around an opaque inner mesh
  * (tree, V_i, F_i, unit vertex normals, materials_i [V_i,5]).  The outer G-buffer comes from nu_relight_gbuffer run on the outer mesh

@@ -1361,6 +1361,83 @@ extern "C" int nu_relight_thin_cross(const float* d, const float* normal, const 
     return nu_launch_status();
 }
 
+// ------------------------------------------------------------------------------------------------
+// visibility transfer: ONE surface point per single-wave block, all its hemisphere rays in this launch, reduced in the wave.
+// A round is 16 quads = 16 consecutive samples: each quad makes its ray in registers (relight.h) and walks it any-hit on the one stack;
+// lane 0 of the quad leaves the sample's NU_TR_LIVE contributions (zero when occluded) in `red`, and lanes 0 .. NU_TR_LIVE - 1, one per
+// output column, add the round's 16 entries IN SAMPLE ORDER to a register.  No verdict, no ray and no partial sum goes to memory: the
+// point's row is the only store, and its bits depend on nothing but the point, its id, the sample parameters and the mesh.
+// ------------------------------------------------------------------------------------------------
+template <bool DUMP>
+__global__ __launch_bounds__(64) void transfer_bake_kernel(const char* __restrict__ buf, NuBvhLayout L, const float* __restrict__ points,
+                                                           const float* __restrict__ normals, int id0, int S, unsigned seed, float eps,
+                                                           float radius, float* __restrict__ out, unsigned char* __restrict__ vis) {
+    __shared__ int stack[NU_WSTACK][16];
+    __shared__ float red[16][NU_TR_ROW];
+    const int lane = threadIdx.x & 63, sub = lane & 3, q = lane >> 2;
+    const long long i = blockIdx.x;
+    const int id = (int)((unsigned)id0 + (unsigned)blockIdx.x);
+    float p[3], n[3];
+    for (int k = 0; k < 3; ++k) { p[k] = points[i * 3 + k]; n[k] = normals[i * 3 + k]; }
+    float acc = 0.0f;
+    for (int s0 = 0; s0 < S; s0 += 16) {                    // every lane of the wave takes every round: the barriers are uniform
+        const int s = s0 + q;
+        unsigned bits[2];
+        float o[3], d[3];
+        nu_transfer_uniforms(id, seed, S, s, bits);
+        nu_transfer_ray(p, n, eps, bits, o, d);
+        int found, fid;
+        float t;
+        nu_walk_quad(stack, q, sub, buf, L, o, d, 0.0f, radius, true, found, fid, t);
+        if (sub == 0) {
+            float c[NU_TR_LIVE];
+            nu_transfer_contrib(d, c);
+#pragma unroll
+            for (int k = 0; k < NU_TR_LIVE; ++k) red[q][k] = found ? 0.0f : c[k];
+            if (DUMP) vis[i * S + s] = found ? 0 : 1;
+        }
+        __syncthreads();
+        if (lane < NU_TR_LIVE) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc = acc + red[r][lane];
+        }
+        __syncthreads();                                    // the next round overwrites red
+    }
+    if (lane < NU_TR_LIVE) red[0][lane] = acc;
+    __syncthreads();
+    if (lane < NU_TR_ROW) {
+        float sum[NU_TR_LIVE];
+#pragma unroll
+        for (int k = 0; k < NU_TR_LIVE; ++k) sum[k] = red[0][k];
+        out[i * NU_TR_ROW + lane] = nu_transfer_finish(sum, n, S, lane);       // one 64-byte row
+    }
+}
+
+static int nu_transfer_launch(const void* bvh, int n_faces, const float* points, const float* normals, int n, int id0, int samples,
+                              int seed, float eps, float radius, float* out, unsigned char* vis, bool dump, hipStream_t stream) {
+    if (n < 0 || n_faces <= 0 || samples < 16 || (samples & 15)) return NU_ERR_ARG;
+    if (!(eps > -3e38f && eps < 3e38f) || !(radius > 0.0f && radius < 3e38f)) return NU_ERR_ARG;
+    if ((long long)n * samples > 0x7fffffffLL) return NU_ERR_ARG;          // the caller chunks over points (nu_transfer_rays' count)
+    if (n == 0) return NU_OK;
+    if (!bvh || !points || !normals || !out || (dump && !vis)) return NU_ERR_ARG;
+    const NuBvhLayout L = nu_bvh_layout(n_faces);
+    if (dump)
+        hipLaunchKernelGGL((transfer_bake_kernel<true>), dim3((unsigned)n), dim3(64), 0, stream, (const char*)bvh, L, points, normals, id0,
+                           samples, (unsigned)seed, eps, radius, out, vis);
+    else
+        hipLaunchKernelGGL((transfer_bake_kernel<false>), dim3((unsigned)n), dim3(64), 0, stream, (const char*)bvh, L, points, normals, id0,
+                           samples, (unsigned)seed, eps, radius, out, vis);
+    return nu_launch_status();
+}
+extern "C" int nu_transfer_bake(const void* bvh, int n_faces, const float* points, const float* normals, int n, int id0, int samples,
+                                int seed, float eps, float radius, float* out, hipStream_t stream) {
+    return nu_transfer_launch(bvh, n_faces, points, normals, n, id0, samples, seed, eps, radius, out, nullptr, false, stream);
+}
+extern "C" int nu_transfer_bake_dump(const void* bvh, int n_faces, const float* points, const float* normals, int n, int id0, int samples,
+                                     int seed, float eps, float radius, float* out, unsigned char* vis, hipStream_t stream) {
+    return nu_transfer_launch(bvh, n_faces, points, normals, n, id0, samples, seed, eps, radius, out, vis, true, stream);
+}
+
 // brute-force closest hit on the device (same triangle test; O(N*F)): cross-check + tiny meshes
 __global__ __launch_bounds__(256) void brute_trace_kernel(const float* __restrict__ V, const int* __restrict__ F, int nf,
                                                           const float* __restrict__ rays, int N, float tmin, float tmax,

@@ -5,7 +5,8 @@
 // traces, the ray nu_relight_shadow_rays dumps and the direction nu_relight_resolve shades are the same bits.
 // Further down: the nested object (nu_rl_surface, nu_rln_interface, nu_rln_leave -- a solid glass shell, one interface) and
 // the thin shell (nu_rlt_cross, nu_rlt_leave -- the wall crossing of the non-zero-thickness stage-2 model, the geometry of
-// s2_shell_core in stage2.hip restated after its sigmoids, with a Schlick factor per face).
+// s2_shell_core in stage2.hip restated after its sigmoids, with a Schlick factor per face).  At the end: visibility transfer
+// (the hemisphere samples of a surface point, its transfer row, the row at a hit point, specular occlusion).
 #pragma once
 #include "nu_common.h"
 
@@ -372,4 +373,106 @@ static __device__ inline void nu_relight_weight(const float* g, int lobe, const 
         const float f0 = 0.04f + (g[10 + c] - 0.04f) * metallic;
         wgt[c] = (f0 + (1.0f - f0) * fc) * k;
     }
+}
+
+// ---- visibility transfer: the hemisphere samples of a surface point, its 16-float transfer row, the row of a hit point ----
+// Transfer row of a point: NU_TR_ROW floats.
+//   [0..8] T_k = (1/S) sum_s V_s Y_k(w_s), order-2 real SH in the order (0,0) (1,-1) (1,0) (1,1) (2,-2) .. (2,2)
+//   [9] ambient occlusion = unoccluded samples / S   [10..12] bent normal (unit)   [13..15] 0
+#define NU_TR_ROW 16
+#define NU_TR_LIVE 13                // columns a sample contributes to: 9 SH values, 1, its direction
+
+// Sample j of M of the point that hashes as `id`: section 20's sequence with ONE lobe -- Hammersley point (j / M, bit-reversed j) as 32-bit
+// fixed point, Cranley-Patterson shift = two hash words of (id, seed), the uniforms are the top 24 bits.  Integers up to bits[0], bits[1].
+static __device__ inline void nu_transfer_uniforms(int id, unsigned seed, int M, int j, unsigned* bits) {
+    const unsigned x1 = (unsigned)(((unsigned long long)(unsigned)j << 32) / (unsigned long long)M);
+    const unsigned x2 = __brev((unsigned)j);
+    unsigned a = nu_rl_fmix32((unsigned)id + 0x9E3779B9u);
+    a = nu_rl_fmix32(a ^ seed);
+    const unsigned h1 = nu_rl_fmix32(a + 1u);
+    const unsigned h2 = nu_rl_fmix32(h1 ^ 0x68E31DA4u);
+    bits[0] = (x1 + h1) >> 8;
+    bits[1] = (x2 + h2) >> 8;
+}
+
+// The ray of those two integers at point p with unit normal n: cosine-weighted direction cos = sqrt(1 - u2), sin = sqrt(u2),
+// phi = 2 pi u1 in nu_rl_frame(n); origin p + eps n.  u2 < 1, so cos > 0: every sample is above the horizon and is traced.
+static __device__ inline void nu_transfer_ray(const float* p, const float* n, float eps, const unsigned* bits, float* o, float* d) {
+    const float u1 = (float)bits[0] * 5.9604644775390625e-08f, u2 = (float)bits[1] * 5.9604644775390625e-08f;   // 2^-24
+    float t[3], b[3];
+    nu_rl_frame(n, t, b);
+    float sp, cp;
+    sincosf(6.283185307179586f * u1, &sp, &cp);
+    const float ct = sqrtf(1.0f - u2), st = sqrtf(u2);
+    const float lx = st * cp, ly = st * sp;
+    for (int k = 0; k < 3; ++k) {
+        d[k] = (lx * t[k] + ly * b[k]) + ct * n[k];
+        o[k] = p[k] + eps * n[k];
+    }
+}
+
+// Order-2 real spherical harmonics of a direction, the order and constants of the row above.
+static __device__ inline void nu_transfer_sh9(const float* w, float* y) {
+    const float x = w[0], yy = w[1], z = w[2];
+    y[0] = 0.282095f;
+    y[1] = 0.488603f * yy;
+    y[2] = 0.488603f * z;
+    y[3] = 0.488603f * x;
+    y[4] = 1.092548f * (x * yy);
+    y[5] = 1.092548f * (yy * z);
+    y[6] = 0.315392f * (3.0f * (z * z) - 1.0f);
+    y[7] = 1.092548f * (x * z);
+    y[8] = 0.546274f * (x * x - yy * yy);
+}
+
+// What an unoccluded sample of direction w adds to the NU_TR_LIVE sums of its point.
+static __device__ inline void nu_transfer_contrib(const float* w, float* c) {
+    nu_transfer_sh9(w, c);
+    c[9] = 1.0f;
+    c[10] = w[0]; c[11] = w[1]; c[12] = w[2];
+}
+
+// Output column c (0 .. NU_TR_ROW - 1) of a row from the NU_TR_LIVE sums over S samples.
+static __device__ inline float nu_transfer_finish(const float* sum, const float* n, int S, int c) {
+    if (c < 10) return sum[c] / (float)S;
+    if (c >= NU_TR_LIVE) return 0.0f;
+    const float len = sqrtf((sum[10] * sum[10] + sum[11] * sum[11]) + sum[12] * sum[12]);
+    return len < 1e-12f ? n[c - 10] : sum[c] / len;
+}
+
+// Barycentric coordinates (u, v) of a point x of the plane of triangle (v0, v1, v2): x = v0 + u (v1 - v0) + v (v2 - v0), least squares.
+// THE formula of the occluded resolve (the float64 oracle restates it); a face without area gives u = v = 0, vertex 0.
+static __device__ inline void nu_transfer_bary(const float* x, const float* v0, const float* v1, const float* v2, float& u, float& v) {
+    float e1[3], e2[3], tv[3];
+    for (int k = 0; k < 3; ++k) { e1[k] = v1[k] - v0[k]; e2[k] = v2[k] - v0[k]; tv[k] = x[k] - v0[k]; }
+    const float d11 = nu_rl_dot3(e1, e1), d12 = nu_rl_dot3(e1, e2), d22 = nu_rl_dot3(e2, e2);
+    const float t1 = nu_rl_dot3(tv, e1), t2 = nu_rl_dot3(tv, e2);
+    const float den = d11 * d22 - d12 * d12;
+    u = 0.0f; v = 0.0f;
+    if (den > 0.0f) {
+        u = (d22 * t1 - d12 * t2) / den;
+        v = (d11 * t2 - d12 * t1) / den;
+    }
+}
+
+// The NU_TR_LIVE live columns of the transfer at hit point x of face `id`: r0 + u (r1 - r0) + v (r2 - r0) of the three vertex rows (rows
+// that agree in a column give that value exactly), the bent normal renormalised (vertex 0's when the mix has no length).
+static __device__ inline void nu_transfer_at(const float* __restrict__ V, const int* __restrict__ F, const float* __restrict__ transfer,
+                                             int id, const float* x, float* row) {
+    const int i0 = F[id * 3LL], i1 = F[id * 3LL + 1], i2 = F[id * 3LL + 2];
+    float v0[3], v1[3], v2[3], u, v;
+    for (int k = 0; k < 3; ++k) { v0[k] = V[i0 * 3LL + k]; v1[k] = V[i1 * 3LL + k]; v2[k] = V[i2 * 3LL + k]; }
+    nu_transfer_bary(x, v0, v1, v2, u, v);
+    const float* r0 = transfer + (long long)i0 * NU_TR_ROW;
+    const float* r1 = transfer + (long long)i1 * NU_TR_ROW;
+    const float* r2 = transfer + (long long)i2 * NU_TR_ROW;
+    for (int k = 0; k < NU_TR_LIVE; ++k) row[k] = (r0[k] + u * (r1[k] - r0[k])) + v * (r2[k] - r0[k]);
+    const float len = sqrtf((row[10] * row[10] + row[11] * row[11]) + row[12] * row[12]);
+    for (int k = 10; k < NU_TR_LIVE; ++k) row[k] = len > 0.0f ? row[k] / len : r0[k];
+}
+
+// Specular occlusion of Lagarde & de Rousiers 2014: clamp((NoV + ao)^(2^(-16 rho - 1)) - 1 + ao, 0, 1); exactly 1 at ao = 1.
+static __device__ inline float nu_transfer_spec_occlusion(float nov, float ao, float rho) {
+    const float p = powf(fminf(fmaxf(nov, 0.0f), 1.0f) + ao, exp2f(-16.0f * rho - 1.0f));
+    return fminf(fmaxf((p - 1.0f) + ao, 0.0f), 1.0f);
 }

@@ -280,3 +280,103 @@ extern "C" int nu_relight_splitsum(const float* gbuf, const int* pix, int n_pix,
                        pw, lv, (const float4*)diffuse, dh, dw, fg, out);
     return nu_launch_status();
 }
+
+// ---- visibility transfer: the shadowed split-sum resolve and the test entry of the bake's rays ---------------------------
+// exactly the rays nu_transfer_bake makes (the same device functions), written out: rays [n * samples, 6], bits [n * samples, 2] = the
+// two 24-bit sample integers
+__global__ __launch_bounds__(256) void transfer_rays_kernel(const float* __restrict__ points, const float* __restrict__ normals, int n,
+                                                            int id0, int S, unsigned seed, float eps, float* __restrict__ rays,
+                                                            int* __restrict__ bits_out) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= (long long)n * S) return;
+    const int i = (int)(r / S), s = (int)(r - (long long)i * S);
+    float p[3], nn[3], o[3], d[3];
+    for (int k = 0; k < 3; ++k) { p[k] = points[i * 3LL + k]; nn[k] = normals[i * 3LL + k]; }
+    unsigned bits[2];
+    nu_transfer_uniforms((int)((unsigned)id0 + (unsigned)i), seed, S, s, bits);
+    nu_transfer_ray(p, nn, eps, bits, o, d);
+    for (int k = 0; k < 3; ++k) { rays[r * 6 + k] = o[k]; rays[r * 6 + 3 + k] = d[k]; }
+    if (bits_out) { bits_out[r * 2] = (int)bits[0]; bits_out[r * 2 + 1] = (int)bits[1]; }
+}
+
+extern "C" int nu_transfer_rays(const float* points, const float* normals, int n, int id0, int samples, int seed, float eps, float* rays,
+                                int* bits, hipStream_t stream) {
+    if (n < 0 || samples < 16 || (samples & 15) || !(eps > -3e38f && eps < 3e38f)) return NU_ERR_ARG;
+    const long long N = (long long)n * samples;
+    if (N > 0x7fffffffLL) return NU_ERR_ARG;
+    if (N == 0) return NU_OK;
+    if (!points || !normals || !rays) return NU_ERR_ARG;
+    hipLaunchKernelGGL(transfer_rays_kernel, dim3((unsigned)nu_cdivl(N, 256)), dim3(256), 0, stream, points, normals, n, id0, samples,
+                       (unsigned)seed, eps, rays, bits);
+    return nu_launch_status();
+}
+
+// One thread per listed hit pixel: nu_relight_splitsum's two terms D and Sp from its device functions in its order, then the transfer
+// row at the hit point (relight.h) shadows them:  NU_OCC_AO  ao D + so Sp;  NU_OCC_SH  (1 - m) a max(sum_k T_k L_k, 0) + so Sp.
+__global__ __launch_bounds__(256) void relight_splitsum_occluded_kernel(const float* __restrict__ gbuf, const int* __restrict__ face,
+                                                                        const int* __restrict__ pix, int n_pix, const float* __restrict__ V,
+                                                                        const int* __restrict__ F, const float* __restrict__ transfer,
+                                                                        const float4* __restrict__ envsh, int mode,
+                                                                        const float4* __restrict__ pyr, int L, int ph, int pw, RlLevels lv,
+                                                                        const float4* __restrict__ diffuse, int dh, int dw,
+                                                                        const float* __restrict__ fg, float* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_pix) return;
+    const long long row = pix[i];
+    float g[NU_RL_ROW];
+#pragma unroll
+    for (int k = 0; k < NU_RL_ROW; k += 4) {
+        const float4 q = *(const float4*)(gbuf + row * NU_RL_ROW + k);
+        g[k] = q.x; g[k + 1] = q.y; g[k + 2] = q.z; g[k + 3] = q.w;
+    }
+    const float* n = g + 7;
+    const float* v = g + 15;
+    const float m = g[13], rho = g[14];
+    const float nov = nu_rl_dot3(n, v);
+    float r[3], ld[3], ls[3], A, B;
+    for (int c = 0; c < 3; ++c) r[c] = (2.0f * nov) * n[c] - v[c];
+    nu_relight_env(diffuse, dh, dw, n, ld);
+    nu_rl_pyramid(pyr, L, ph, pw, lv, r, rho, ls);
+    nu_rl_fg(fg, fminf(fmaxf(nov, 0.f), 1.f), fminf(fmaxf(rho, 0.f), 1.f), A, B);
+    float tr[NU_TR_LIVE];
+    nu_transfer_at(V, F, transfer, face[row], g + 1, tr);
+    const float ao = tr[9];
+    const float so = nu_transfer_spec_occlusion(nov, ao, rho);
+    float4 o;
+    float rgb[3];
+    for (int c = 0; c < 3; ++c) {
+        const float f0 = 0.04f * (1.0f - m) + m * g[10 + c];
+        const float kd = (1.0f - m) * g[10 + c];
+        const float sp = (f0 * A + B) * ls[c];
+        if (mode == NU_OCC_AO) {
+            rgb[c] = ao * (kd * ld[c]) + so * sp;
+        } else {
+            float e = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                const float4 lk = envsh[k];
+                e = e + tr[k] * (c == 0 ? lk.x : (c == 1 ? lk.y : lk.z));
+            }
+            rgb[c] = kd * fmaxf(e, 0.0f) + so * sp;
+        }
+    }
+    o.x = rgb[0]; o.y = rgb[1]; o.z = rgb[2]; o.w = 1.0f;
+    *(float4*)(out + row * 4) = o;
+}
+
+extern "C" int nu_relight_splitsum_occluded(const float* gbuf, const int* face, const int* pix, int n_pix, const float* V, const int* F,
+                                            const float* transfer, const float* envsh, int mode, const float* pyr, int L, int ph, int pw,
+                                            const float* levels, const float* diffuse, int dh, int dw, const float* fg, float* out,
+                                            hipStream_t stream) {
+    if (n_pix < 0 || L < 1 || L > NU_ENV_MAX_LOBES || ph <= 0 || pw <= 0 || dh <= 0 || dw <= 0) return NU_ERR_ARG;
+    if (mode != NU_OCC_AO && mode != NU_OCC_SH) return NU_ERR_ARG;
+    if (!gbuf || !face || (n_pix > 0 && !pix) || !V || !F || !transfer || (mode == NU_OCC_SH && !envsh) || !pyr || !levels || !diffuse || !fg
+        || !out)
+        return NU_ERR_ARG;
+    RlLevels lv;
+    if (!nu_rl_levels(levels, L, lv)) return NU_ERR_ARG;
+    if (n_pix == 0) return NU_OK;
+    hipLaunchKernelGGL(relight_splitsum_occluded_kernel, dim3(nu_cdiv(n_pix, 256)), dim3(256), 0, stream, gbuf, face, pix, n_pix, V, F,
+                       transfer, (const float4*)envsh, mode, (const float4*)pyr, L, ph, pw, lv, (const float4*)diffuse, dh, dw, fg, out);
+    return nu_launch_status();
+}

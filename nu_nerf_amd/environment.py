@@ -108,6 +108,26 @@ def latlong_dirs(h, w):
     return np.ascontiguousarray(d.reshape(h * w, 3), dtype=np.float32)
 
 
+def project_sh(env):
+    """Order-2 spherical-harmonic coefficients float64 [9,3] of a lat-long map [h,w,3] (transfer.sh_basis' order and
+    constants): L_k = (4 pi / sum_j w_j) sum_j w_j Y_k(s_j) rgb_j over the texel centres s_j of latlong_dirs with w = sin theta.  On the
+    host in float64: a 256 x 512 map is a 9 x 131 072 x 3 product."""
+    from .transfer import sh_basis
+    env = np.asarray(env, np.float64)
+    if env.ndim != 3 or env.shape[2] != 3 or env.shape[0] < 1 or env.shape[1] < 1:
+        raise ValueError(f"environment map must be [H,W,3], got {env.shape}")
+    if not np.isfinite(env).all():
+        raise ValueError("environment map has non-finite values")
+    h, w = env.shape[:2]
+    theta = (np.arange(h, dtype=np.float64) + 0.5) * np.pi / h
+    phi = 2.0 * np.pi * (0.5 - (np.arange(w, dtype=np.float64) + 0.5) / w)
+    st, ct = np.sin(theta)[:, None], np.cos(theta)[:, None]
+    dirs = np.stack([st * np.cos(phi)[None], st * np.sin(phi)[None], np.broadcast_to(ct, (h, w))], -1)      # latlong_dirs before rounding
+    wgt = np.repeat(np.sin(theta), w)
+    Y = sh_basis(dirs.reshape(h * w, 3))
+    return (4.0 * np.pi / wgt.sum()) * ((Y * wgt[:, None]).T @ env.reshape(h * w, 3))
+
+
 def environment_map(renderer, h=256, w=512, roughness=0.0, point=None, which=None, probe=False):
     """The learned illumination as a lat-long map, float32 numpy [h,w,3] (latlong_dirs' convention, linear radiance).  A sequence of
     roughness values gives the pyramid [L,h,w,3], still in one launch.  point: where the map is seen from (default the origin; it

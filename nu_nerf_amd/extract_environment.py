@@ -1,5 +1,5 @@
 """python -m nu_nerf_amd.extract_environment --cfg CFG [--ckpt PATH] [--stage2] [--which outer|inner] [--height H] [--width W]
-[--roughness R ...] [--point X Y Z] [--probe] [--out DIR]
+[--roughness R ...] [--point X Y Z] [--probe] [--sh] [--out DIR]
 
 The illumination a trained model learned, exported as a lat-long environment map: the renderer named by the config loads
 data/model/{name}/model.pth (train_glue.save_checkpoint format, as extract_materials does) and the light predictors are evaluated at
@@ -12,6 +12,8 @@ of env.npy -- and prints one JSON line (shape, min / max / mean radiance, the pa
 --point: where the environment is seen from (default the origin; with `sphere_direction` the outer light depends on it).  --probe:
 the blended light at --point (indirect light, occlusion and direct light) instead of the direct light alone.  --stage2: a stage-2
 config; --which outer (default) evaluates the stage-1 networks the model carries, --which inner the inner shading network's.
+--sh also writes env_sh.npy [9,3], the order-2 spherical-harmonic coefficients of env.npy (environment.project_sh), which
+relight --transfer --occlusion sh reads.
 """
 import argparse
 import json
@@ -30,6 +32,7 @@ def parse_args(argv=None):
     ap.add_argument('--roughness', type=float, nargs='+', default=[0.0, 0.25, 0.5, 0.75, 1.0], help="roughness levels of the pyramid")
     ap.add_argument('--point', type=float, nargs=3, default=None, metavar=('X', 'Y', 'Z'), help="where the map is seen from (default the origin)")
     ap.add_argument('--probe', action='store_true', help="the blended light at --point instead of the direct light")
+    ap.add_argument('--sh', action='store_true', default=False, help="also write env_sh.npy, the SH coefficients [9,3] of env.npy")
     ap.add_argument('--out', type=str, default=None, help="output directory (default data/environment/{name}-{step})")
     flags = ap.parse_args(argv)
     if flags.which == 'inner' and not flags.stage2:
@@ -50,7 +53,7 @@ def main(argv=None):
     import numpy as np
     import torch
     import yaml
-    from .environment import environment_map, write_hdr
+    from .environment import environment_map, project_sh, write_hdr
     from .extract_mesh import _renderer
     from .relight import to_srgb8, write_png
     from .train_glue import load_checkpoint
@@ -81,6 +84,9 @@ def main(argv=None):
     write_hdr(paths['hdr'], env)
     np.save(paths['pyramid'], pyramid)
     np.save(paths['roughness'], levels)
+    if flags.sh:
+        paths['sh'] = os.path.join(out, 'env_sh.npy')
+        np.save(paths['sh'], project_sh(env))
     rgba = torch.cat([torch.from_numpy(env), torch.ones(flags.height, flags.width, 1)], -1)
     write_png(paths['png'], to_srgb8(rgba))
     print(json.dumps({'shape': list(pyramid.shape), 'roughness': [float(r) for r in levels], 'min': float(env.min()),

@@ -1,5 +1,5 @@
 """python -m nu_nerf_amd.relight --mesh PLY --material DIR --hdr FILE --name NAME [--trans] [--num 360 --width 800 --height 800
---samples 1024 --cam_dist 3.0 --azimuth 0 --elevation 45] [--splitsum [--pyramid DIR | --levels R ...]] [--inner PLY --inner-material DIR (--ior VALUE_OR_DIR | --shell DIR_OR_PAIR [--shell-curvature FILE])]
+--samples 1024 --cam_dist 3.0 --azimuth 0 --elevation 45] [--splitsum [--pyramid DIR | --levels R ...] [--transfer DIR [--occlusion ao|sh]]] [--inner PLY --inner-material DIR (--ior VALUE_OR_DIR | --shell DIR_OR_PAIR [--shell-curvature FILE])]
 
 relight.py + blender_backend/relight_backend.py on the GPU: the extracted mesh, the per-vertex DIR/metallic.npy, roughness.npy and
 albedo.npy that extract_materials writes and a lat-long HDR environment map are rendered from the reference's camera orbit
@@ -25,6 +25,10 @@ prefiltered roughness pyramid -- no sampling, no noise, no shadows: a frame is i
 map is prefiltered at --levels (default 0 .25 .5 .75 1; environment.prefilter); with --pyramid DIR it reads env_pyramid.npy,
 roughness.npy and, if present, env_diffuse.npy (otherwise the diffuse map is the level of roughness 1), so a directory written by
 extract_environment or prefilter_environment works as it is.  --samples, --seed and --chunk are not used; --inner is refused.
+--transfer DIR: the per-vertex ao.npy, bent_normal.npy and transfer.npy that `python -m nu_nerf_amd.bake_transfer` wrote for this mesh
+shadow the frame -- --occlusion ao (default) darkens the diffuse light by the ambient occlusion, sh lights it through
+the order-2 transfer vector against the environment's SH coefficients (DIR/env_sh.npy of --pyramid if present, otherwise projected
+from its env.npy or its level of lowest roughness; from --hdr); both scale the specular light by the specular occlusion.
 """
 import argparse
 import os
@@ -376,12 +380,48 @@ def splitsum_resolve(gbuf, pix, pyr, levels, diffuse, out):
     return out
 
 
-def relight_splitsum_linear(V, F, materials, pyramid, levels, diffuse, poses, h, w, rows=None, images=1, K=None):
+OCCLUSION = {'ao': 0, 'sh': 1}  # NU_OCC_AO, NU_OCC_SH
+
+
+def splitsum_resolve_occluded(scene, gbuf, face, pix, pyr, levels, diffuse, transfer, env_sh, mode, out):
+    """out [rows of gbuf, 4] = the split-sum colour of the listed hit pixels shadowed by `transfer` [Nv,16] (device; transfer.py): mode
+    'ao' scales the diffuse term by the ambient occlusion, 'sh' replaces it by the dot product of the transfer vector with env_sh [9,4]
+    (device); both scale the specular term by the specular occlusion.  face: the G-buffer pass's face ids."""
+    from . import _lib as L
+    lv, nl = _levels_arg(levels)
+    L.load().nu_relight_splitsum_occluded(L.ptr(gbuf), L.ptr(face), L.ptr(pix), int(pix.shape[0]), L.ptr(scene.V), L.ptr(scene.F),
+                                          L.ptr(transfer), L.ptr(env_sh), OCCLUSION[mode], L.ptr(pyr), nl, int(pyr.shape[1]),
+                                          int(pyr.shape[2]), lv, L.ptr(diffuse), int(diffuse.shape[0]), int(diffuse.shape[1]),
+                                          L.ptr(fg_table(gbuf.device)), L.ptr(out), L.stream())
+    return out
+
+
+def _transfer_args(scene, transfer, occlusion, env_sh):
+    """The device arrays of the shadowed resolve: transfer float32 [Nv,16] (a device tensor is taken as it is) and env_sh [9,4] or None."""
+    import torch
+    from .transfer import ROW as TR_ROW, pack_env_sh
+    if occlusion not in OCCLUSION:
+        raise ValueError(f"occlusion must be 'ao' or 'sh', got {occlusion!r}")
+    if occlusion == 'sh' and env_sh is None:
+        raise ValueError("occlusion='sh' needs env_sh, the SH coefficients [9,3] of the environment (environment.project_sh)")
+    t = transfer if torch.is_tensor(transfer) else torch.from_numpy(np.ascontiguousarray(transfer, np.float32))
+    t = t.detach().to(device=scene.device, dtype=torch.float32).contiguous()
+    if tuple(t.shape) != (int(scene.V.shape[0]), TR_ROW):
+        raise ValueError(f"transfer must be [{int(scene.V.shape[0])},{TR_ROW}] (one row per vertex), got {tuple(t.shape)}")
+    sh = None if env_sh is None else torch.from_numpy(pack_env_sh(env_sh)).to(scene.device)
+    return t, sh
+
+
+def relight_splitsum_linear(V, F, materials, pyramid, levels, diffuse, poses, h, w, rows=None, images=1, K=None, transfer=None,
+                            occlusion='ao', env_sh=None):
     """Linear radiance float32 [n,h,w,4] (alpha 1 on hit pixels, 0 elsewhere) of the split-sum model the networks were trained under:
     (1 - metallic) albedo Ld(n) + (F0 A + B) L(reflect(v, n), roughness), L from the prefiltered `pyramid` [L,ph,pw,3] at the roughness
     `levels` [L], Ld from `diffuse` [dh,dw,3], (A, B) from the shipped table.  No sampling, no visibility, no interreflection: a frame is
     its G-buffer pass and one resolve launch.  The Scene, cameras, G-buffer and hit list are relight_linear's; the result does not depend
-    on `rows` / `images`, bit for bit."""
+    on `rows` / `images`, bit for bit.
+    transfer: float32 [Nv,16] rows of transfer.bake_transfer for the mesh's vertices -- the frame then has contact shadows and
+    self-occlusion: occlusion='ao' darkens the diffuse term by the ambient occlusion, 'sh' lights it with the transfer
+    vector against env_sh [9,3] (environment.project_sh of the environment); None is the unshadowed path above, untouched."""
     import torch
     from .mask_render import _cams
     if images < 1 or (rows is not None and rows < 1):
@@ -390,6 +430,7 @@ def relight_splitsum_linear(V, F, materials, pyramid, levels, diffuse, poses, h,
     dev = scene.device
     pyr, lv = pack_pyramid(pyramid, levels)
     pyr, dif = torch.from_numpy(pyr).to(dev), torch.from_numpy(pack_env(diffuse)).to(dev)
+    tr, sh = (None, None) if transfer is None else _transfer_args(scene, transfer, occlusion, env_sh)
     poses = np.asarray(poses.cpu() if torch.is_tensor(poses) else poses, np.float64).reshape(-1, 3, 4)
     K = intrinsics(h, w) if K is None else np.asarray(K, np.float64)
     cams = _cams(K.astype(np.float32), poses.astype(np.float32), dev)
@@ -401,7 +442,10 @@ def relight_splitsum_linear(V, F, materials, pyramid, levels, diffuse, poses, h,
             nr = min(rows, h - y0)
             face, gbuf = gbuffer(scene, cams[i0:i0 + ni], h, w, i0, y0, nr)
             piece = torch.zeros(ni * nr * w, 4, dtype=torch.float32, device=dev)
-            splitsum_resolve(gbuf, hit_pixels(face), pyr, lv, dif, piece)
+            if transfer is None:
+                splitsum_resolve(gbuf, hit_pixels(face), pyr, lv, dif, piece)
+            else:
+                splitsum_resolve_occluded(scene, gbuf, face, hit_pixels(face), pyr, lv, dif, tr, sh, occlusion, piece)
             out[i0:i0 + ni, y0:y0 + nr] = piece.reshape(ni, nr, w, 4)
     return out
 
@@ -433,6 +477,23 @@ def load_pyramid_dir(directory):
 
 
 # ---- the nested object ------------------------------------------------------------------------------------------------
+def load_env_sh(directory):
+    """(env_sh float64 [9,3], the file it came from) of a pyramid directory: env_sh.npy if present, otherwise the projection
+    (environment.project_sh) of env.npy or, without one, of the pyramid level of lowest roughness."""
+    from .environment import project_sh
+    path = os.path.join(directory, 'env_sh.npy')
+    if os.path.exists(path):
+        sh = np.asarray(np.load(path), np.float64)
+        if sh.shape != (9, 3):
+            raise ValueError(f"{path}: expected [9,3], got {sh.shape}")
+        return sh, path
+    path = os.path.join(directory, 'env.npy')
+    if os.path.exists(path):
+        return project_sh(np.load(path)), path + ' (projected)'
+    pyramid, levels, _ = load_pyramid_dir(directory)
+    return project_sh(pyramid[0]), os.path.join(directory, 'env_pyramid.npy') + f' level of roughness {float(levels[0]):g} (projected)'
+
+
 MAX_SEGMENTS = 4                # NU_RLN_MAX_SEGMENTS: interior segments of a camera path before the pixel counts as dark
 CHAIN = 12                      # floats per chain record (include/nu_nerf.h)
 DARK, INNER, EXIT = 0, 1, 2     # terminal kinds of a pixel's interior chain
@@ -689,6 +750,10 @@ def parse_args(argv=None):
     ap.add_argument('--pyramid', type=str, default=None,
                     help="with --splitsum: a directory with env_pyramid.npy and roughness.npy (extract_environment, prefilter_environment) instead of --hdr")
     ap.add_argument('--levels', type=float, nargs='+', default=None, help="with --splitsum --hdr: roughness levels of the pyramid (default 0 .25 .5 .75 1)")
+    ap.add_argument('--transfer', type=str, default=None,
+                    help="with --splitsum: a directory with transfer.npy, ao.npy and bent_normal.npy of the mesh (bake_transfer): shadowed frames")
+    ap.add_argument('--occlusion', choices=tuple(OCCLUSION), default=None,
+                    help="with --transfer: ao (default) darkens the diffuse light by the ambient occlusion, sh lights it through the transfer vector")
     ap.add_argument('--name', type=str, required=True, help="frames go to data/relight/NAME")
     ap.add_argument('--trans', action='store_true', default=False, help="turn the mesh +90 degrees about x")
     ap.add_argument('--inner', type=str, default=None, help="inner mesh (PLY): --mesh is then the transparent shell around it")
@@ -718,6 +783,10 @@ def parse_args(argv=None):
         ap.error("--num, --width, --height and --chunk must be >= 1")
     if not flags.splitsum and (flags.pyramid is not None or flags.levels is not None):
         ap.error("--pyramid and --levels need --splitsum")
+    if flags.transfer is not None and (not flags.splitsum or flags.inner is not None):
+        ap.error("--transfer shadows the split-sum frame of the plain object: it needs --splitsum and excludes --inner")
+    if flags.occlusion is not None and flags.transfer is None:
+        ap.error("--occlusion needs --transfer")
     if flags.splitsum:
         if flags.inner is not None:
             ap.error("--splitsum renders the plain object only: nested and thin-shell scenes (--inner) keep the Monte-Carlo path")
@@ -849,13 +918,24 @@ def main(argv=None):
             from .environment import DEFAULT_LEVELS, prefilter
             levels = np.asarray(flags.levels or DEFAULT_LEVELS, np.float32)
             pyramid, diffuse, _ = prefilter(read_hdr(flags.hdr), levels)
+        kw = {}
+        if flags.transfer is not None:
+            from .transfer import load_transfer_dir
+            kw = {'transfer': load_transfer_dir(flags.transfer, len(V)), 'occlusion': flags.occlusion or 'ao'}
+            if kw['occlusion'] == 'sh':
+                if flags.pyramid is not None:
+                    kw['env_sh'], source = load_env_sh(flags.pyramid)
+                else:
+                    from .environment import project_sh
+                    kw['env_sh'], source = project_sh(read_hdr(flags.hdr)), flags.hdr
+                print(f'--occlusion sh: environment SH coefficients from {source}')
     else:
         env = read_hdr(flags.hdr)
     poses = camera_in_mesh_frame(relighting_poses(flags.num, flags.azimuth, flags.elevation, flags.cam_dist))
     K = intrinsics(flags.height, flags.width, flags.focal_mm, flags.sensor_mm)
     for k in todo:
         if flags.splitsum:
-            img = relight_splitsum(scene, None, None, pyramid, levels, diffuse, poses[k:k + 1], flags.height, flags.width, K=K)
+            img = relight_splitsum(scene, None, None, pyramid, levels, diffuse, poses[k:k + 1], flags.height, flags.width, K=K, **kw)
         elif flags.inner is None:
             img = relight(scene, None, None, env, poses[k:k + 1], flags.height, flags.width, flags.samples, flags.seed, flags.chunk, K=K, img0=k)
         else:
