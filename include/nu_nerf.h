@@ -494,6 +494,48 @@ int nu_relight_splitsum_occluded(const float* gbuf, const int* face, const int* 
                                  hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Texture atlas of the relightable asset (the project's own, the reference has no counterpart).  All launches
+ * on `stream`, one thread per item, no allocation, no LDS, no atomics, no workspace.
+ * The atlas of (n_faces, size = T, pad): a square of T x T texels, texel (x, y) at row y, column x.  cols = ceil(sqrt(ceil(n_faces / 2))),
+ * c = T / cols (integer), L = c - 3 - 3 pad; cell k = f >> 1 of face f has its origin at ((k % cols) c, (k / cols) c).  With (i, j) the
+ * cell-local texel: the lower face 2k owns i + j <= c - 2, the upper face 2k + 1 owns i + j >= c and lives in the point-mirrored frame
+ * (s, t) = (c - 1 - i, c - 1 - j) (the lower face: (s, t) = (i, j)); the diagonal i + j = c - 1, texels outside the cols x cols cells and
+ * the halves of faces >= n_faces are owned by nobody.  In its frame a face has its vertices 0, 1, 2 at (pad, pad), (pad + L, pad),
+ * (pad, pad + L), and an owned texel stands for the EXTRAPOLATED barycentrics b1 = (s - pad) / L, b2 = (t - pad) / L, b0 = (1 - b1) - b2
+ * (integers converted to fp32, one division each).
+ *   nu_atlas_texels    rows [y0, y0 + rows) of the atlas.  texel [rows, T, 4] is WRITTEN: the surface point (b0 v0 + b1 v1) + b2 v2 of the
+ *                      owning face (each operation one fp32 rounding, in this order: a corner texel holds its vertex's bits) and the
+ *                      face id as int bits in the fourth lane; an unowned texel, and one whose face names a vertex outside
+ *                      [0, n_verts), is (0, 0, 0, -1).  vnormals [n_verts,3] (unit; may be NULL together with normal): normal
+ *                      [rows, T, 4] = the same mix of the vertex normals divided by its length, 0 in the fourth lane; a mix of length 0
+ *                      or >= 1e30 (or NaN) gives the unit geometric normal (v1 - v0) x (v2 - v0) instead, zero when that has no length
+ *                      either; zero on unowned texels.  A texel's bits do not depend on y0 / rows.
+ *   nu_atlas_sample    out [n, 5] = the bilinear lookup at barycentrics uv [n, 2] = (u, v) (weights of vertices 1 and 2) of face [n];
+ *                      a face outside [0, n_faces) gives zeros.  atlas = two planes [2, T, T, 4]: (albedo r, g, b, metallic), then
+ *                      (roughness, three spare lanes); out = albedo, metallic, roughness.  u = clamp(u, 0, 1), v = clamp(v, 0, 1 - u),
+ *                      s = pad + u L, t = min(pad + v L, (2 pad + L) - s), taps floor(s), floor(s) + 1, floor(t), floor(t) + 1 in the
+ *                      face's frame, fractions fs, ft; value = lo + ft (hi - lo), lo = t00 + fs (t10 - t00), hi = t01 + fs (t11 - t01),
+ *                      where fs == 0 (ft == 0) leaves the +1 taps out altogether.  Every tap that takes part has s + t <= c - 2 - pad:
+ *                      it is owned by the face, whatever (u, v).
+ *   nu_atlas_gbuffer   pix [n_pix] = rows of a G-buffer of nu_relight_gbuffer (gbuf [*, 20], face [*]) for the mesh V, F.  Per listed row
+ *                      whose face id is in [0, n_faces): (u, v) of the stored hit point in its face by the formula of
+ *                      nu_relight_splitsum_occluded above, nu_atlas_sample's lookup, and columns 10..14 of the row (albedo, metallic,
+ *                      roughness) are OVERWRITTEN.  Every other column, every unlisted row and listed miss rows stay as they are.
+ *   NU_ERR_ARG (all three): n_faces < 1, size < 1 or > NU_ATLAS_MAX_SIZE, pad < 0 or > NU_ATLAS_MAX_PAD, L < 2, n_verts < 1, a negative
+ *   count, rows outside the atlas, a NULL array that is read or written, vnormals without normal or the reverse.  A count of 0
+ *   launches nothing.
+ * --------------------------------------------------------------------------------------------------------- */
+#define NU_ATLAS_CH 5
+#define NU_ATLAS_MAX_SIZE 32768
+#define NU_ATLAS_MAX_PAD 64
+int nu_atlas_texels(const float* V, int n_verts, const int* F, int n_faces, const float* vnormals, int size, int pad, int y0, int rows,
+                    float* texel, float* normal, hipStream_t stream);
+int nu_atlas_sample(const float* atlas, int size, int n_faces, int pad, const int* face, const float* uv, int n, float* out,
+                    hipStream_t stream);
+int nu_atlas_gbuffer(float* gbuf, const int* face, const int* pix, int n_pix, const float* V, int n_verts, const int* F, int n_faces,
+                     const float* atlas, int size, int pad, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Relighting of the NESTED object (the project's own transport, pinned against no other renderer): a
  * transparent outer shell (tree, V_o, F_o, unit vertex normals, index of refraction ior [V_o] >= 1) around an opaque inner mesh
  * (tree, V_i, F_i, unit vertex normals, materials_i [V_i,5]).  The outer G-buffer comes from nu_relight_gbuffer run on the outer mesh

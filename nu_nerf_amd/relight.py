@@ -1,4 +1,4 @@
-"""python -m nu_nerf_amd.relight --mesh PLY --material DIR --hdr FILE --name NAME [--trans] [--num 360 --width 800 --height 800
+"""python -m nu_nerf_amd.relight --mesh PLY --material DIR --hdr FILE --name NAME [--texture DIR] [--trans] [--num 360 --width 800 --height 800
 --samples 1024 --cam_dist 3.0 --azimuth 0 --elevation 45] [--splitsum [--pyramid DIR | --levels R ...] [--transfer DIR [--occlusion ao|sh]]] [--inner PLY --inner-material DIR (--ior VALUE_OR_DIR | --shell DIR_OR_PAIR [--shell-curvature FILE])]
 
 relight.py + blender_backend/relight_backend.py on the GPU: the extracted mesh, the per-vertex DIR/metallic.npy, roughness.npy and
@@ -15,6 +15,10 @@ extract_materials --stage2 wrote; --material is not needed.  The view refracts i
 (DESIGN.md 21).  --trans turns both meshes.  --shell instead of --ior: the shell is the thin glass wall of the non-zero-thickness
 stage-2 model around an air-like cavity: the directory whose shell_ior.npy and shell_thickness.npy [V,1]
 extract_materials --stage2 wrote for such a config, or "IOR,THICKNESS" (two numbers, e.g. "1.45,0.005").
+
+--texture DIR: the atlas.npz `python -m nu_nerf_amd.bake_textures` wrote for this mesh: albedo, metallic and roughness of
+every hit come from the texture atlas, looked up at the hit point, instead of the per-vertex arrays (--material is then not needed).  Works
+in the Monte-Carlo and the --splitsum path, also with --transfer; not with --inner.
 
 --hdr takes a Radiance .hdr (RGBE, flat or run-length scanlines) or a .npy float [H,W,3]; the map is z up in the mesh's frame.
 --focal_mm / --sensor_mm: Blender's default camera (50 mm on a 36 mm sensor fitted to the larger image side).  --seed, --chunk
@@ -164,9 +168,11 @@ def pack_env(env):
 # ---- device passes -----------------------------------------------------------------------------------------------------------------------
 class Scene:
     """Mesh + LBVH + what the G-buffer pass interpolates: unit vertex normals [V,3] and materials [V,5] = albedo, metallic, roughness.
-    materials: a dict with 'albedo' [V,3], 'metallic' [V,1], 'roughness' [V,1] (the arrays extract_materials writes) or one [V,5]."""
+    materials: a dict with 'albedo' [V,3], 'metallic' [V,1], 'roughness' [V,1] (the arrays extract_materials writes) or one [V,5].
+    texture (optional): a texture atlas of the mesh's faces (texture.bake_textures / load_textures / pack_atlas) that
+    relight_linear and relight_splitsum_linear shade from instead; materials may then be None (zeros: every hit row is overwritten)."""
 
-    def __init__(self, V, F, materials, device=None):
+    def __init__(self, V, F, materials, device=None, texture=None):
         import torch
         from .lbvh import LBVH, vertex_normals_and_curvature
         dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
@@ -176,7 +182,9 @@ class Scene:
             raise ValueError(f"mesh must be V [Nv,3], F [Nf,3], got {tuple(V.shape)} {tuple(F.shape)}")
         if F.numel() and (int(F.min()) < 0 or int(F.max()) >= V.shape[0]):
             raise ValueError("face index out of range")
-        if isinstance(materials, dict):
+        if materials is None and texture is not None:
+            m = np.zeros((V.shape[0], 5), np.float32)
+        elif isinstance(materials, dict):
             m = np.concatenate([np.asarray(materials['albedo'], np.float32).reshape(-1, 3),
                                 np.asarray(materials['metallic'], np.float32).reshape(-1, 1),
                                 np.asarray(materials['roughness'], np.float32).reshape(-1, 1)], 1)
@@ -189,6 +197,7 @@ class Scene:
         self.normals = vertex_normals_and_curvature(V, F)[0].to(dev).contiguous()
         self.materials = torch.from_numpy(np.ascontiguousarray(m)).to(dev)
         self.device = dev
+        self.texture = None if texture is None else _packed_texture(self, texture)
 
 
 def gbuffer(scene, cams, h, w, img0=0, y0=0, rows=None):
@@ -262,13 +271,31 @@ def _scene(V, F=None, materials=None):
     return V if isinstance(V, Scene) else Scene(V, F, materials)
 
 
+def _packed_texture(scene, texture):
+    """The atlas on the scene's device as the lookup kernels read it (texture.PackedAtlas), checked against the scene's face count."""
+    from .texture import pack_atlas
+    atlas = pack_atlas(texture, device=scene.device)
+    if atlas.n_faces != int(scene.F.shape[0]):
+        raise ValueError(f"texture: the atlas is laid out for {atlas.n_faces} faces, the mesh has {int(scene.F.shape[0])}")
+    if atlas.device != scene.device:
+        raise ValueError(f"texture: the atlas is on {atlas.device}, the scene on {scene.device}")
+    return atlas
+
+
+def _texture_of(scene, texture):
+    """texture= of a relight call: the argument if given, otherwise the Scene's own atlas (None: per-vertex materials)."""
+    return scene.texture if texture is None else _packed_texture(scene, texture)
+
+
 def relight_linear(V, F, materials, env, poses, h, w, samples, seed=0, chunk=256, rows=None, images=1, K=None, img0=0,
-                   eps=ORIGIN_EPS):
+                   eps=ORIGIN_EPS, texture=None):
     """Linear radiance float32 [n,h,w,4] (RGB, alpha 1 on hit pixels and 0 elsewhere) on the device.  poses [n,3,4]: world -> camera in
     the mesh's frame (camera_in_mesh_frame of relighting_poses); K: [3,3] (default intrinsics(h, w)); env [H,W,3]; V may be a Scene.
     Image i is sampled as image img0 + i.  Work is done `images` images x `rows` image rows x `chunk` samples at a time; the result
     does not depend on any of the three, bit for bit.  Device memory besides the mesh, the environment and the result: 100 bytes per
-    pixel of a piece (G-buffer row, face id, hit list) plus at most VIS_BYTES of visibility bytes -- independent of `samples`."""
+    pixel of a piece (G-buffer row, face id, hit list) plus at most VIS_BYTES of visibility bytes -- independent of `samples`.
+    texture: a texture atlas of the mesh (default: the Scene's own, if it has one) -- the material columns of every hit
+    row are then looked up in it at the hit point (texture.texture_gbuffer) before anything is shaded; None without one: untouched."""
     import torch
     from .mask_render import _cams
     samples, chunk = int(samples), int(chunk)
@@ -278,6 +305,7 @@ def relight_linear(V, F, materials, env, poses, h, w, samples, seed=0, chunk=256
         raise ValueError("chunk, rows and images must be >= 1")
     scene = _scene(V, F, materials)
     dev = scene.device
+    tex = _texture_of(scene, texture)
     poses = np.asarray(poses.cpu() if torch.is_tensor(poses) else poses, np.float64).reshape(-1, 3, 4)
     K = intrinsics(h, w) if K is None else np.asarray(K, np.float64)
     cams = _cams(K.astype(np.float32), poses.astype(np.float32), dev)
@@ -290,6 +318,9 @@ def relight_linear(V, F, materials, env, poses, h, w, samples, seed=0, chunk=256
             nr = min(rows, h - y0)
             face, gbuf = gbuffer(scene, cams[i0:i0 + ni], h, w, img0 + i0, y0, nr)
             pix_all = hit_pixels(face)
+            if tex is not None:
+                from .texture import texture_gbuffer
+                texture_gbuffer(scene, face, gbuf, pix_all, tex)
             piece = torch.zeros(ni * nr * w, 4, dtype=torch.float32, device=dev)
             per = max(1, min(VIS_BYTES // min(chunk, samples), (2 ** 31 - 1) // ((min(chunk, samples) + 15) // 16)))
             for p0 in range(0, int(pix_all.shape[0]), per):
@@ -413,7 +444,7 @@ def _transfer_args(scene, transfer, occlusion, env_sh):
 
 
 def relight_splitsum_linear(V, F, materials, pyramid, levels, diffuse, poses, h, w, rows=None, images=1, K=None, transfer=None,
-                            occlusion='ao', env_sh=None):
+                            occlusion='ao', env_sh=None, texture=None):
     """Linear radiance float32 [n,h,w,4] (alpha 1 on hit pixels, 0 elsewhere) of the split-sum model the networks were trained under:
     (1 - metallic) albedo Ld(n) + (F0 A + B) L(reflect(v, n), roughness), L from the prefiltered `pyramid` [L,ph,pw,3] at the roughness
     `levels` [L], Ld from `diffuse` [dh,dw,3], (A, B) from the shipped table.  No sampling, no visibility, no interreflection: a frame is
@@ -421,7 +452,8 @@ def relight_splitsum_linear(V, F, materials, pyramid, levels, diffuse, poses, h,
     on `rows` / `images`, bit for bit.
     transfer: float32 [Nv,16] rows of transfer.bake_transfer for the mesh's vertices -- the frame then has contact shadows and
     self-occlusion: occlusion='ao' darkens the diffuse term by the ambient occlusion, 'sh' lights it with the transfer
-    vector against env_sh [9,3] (environment.project_sh of the environment); None is the unshadowed path above, untouched."""
+    vector against env_sh [9,3] (environment.project_sh of the environment); None is the unshadowed path above, untouched.
+    texture: as relight_linear's -- the hit rows take albedo, metallic and roughness from the atlas before the resolve (either one)."""
     import torch
     from .mask_render import _cams
     if images < 1 or (rows is not None and rows < 1):
@@ -431,6 +463,7 @@ def relight_splitsum_linear(V, F, materials, pyramid, levels, diffuse, poses, h,
     pyr, lv = pack_pyramid(pyramid, levels)
     pyr, dif = torch.from_numpy(pyr).to(dev), torch.from_numpy(pack_env(diffuse)).to(dev)
     tr, sh = (None, None) if transfer is None else _transfer_args(scene, transfer, occlusion, env_sh)
+    tex = _texture_of(scene, texture)
     poses = np.asarray(poses.cpu() if torch.is_tensor(poses) else poses, np.float64).reshape(-1, 3, 4)
     K = intrinsics(h, w) if K is None else np.asarray(K, np.float64)
     cams = _cams(K.astype(np.float32), poses.astype(np.float32), dev)
@@ -442,10 +475,14 @@ def relight_splitsum_linear(V, F, materials, pyramid, levels, diffuse, poses, h,
             nr = min(rows, h - y0)
             face, gbuf = gbuffer(scene, cams[i0:i0 + ni], h, w, i0, y0, nr)
             piece = torch.zeros(ni * nr * w, 4, dtype=torch.float32, device=dev)
+            pix = hit_pixels(face)
+            if tex is not None:
+                from .texture import texture_gbuffer
+                texture_gbuffer(scene, face, gbuf, pix, tex)
             if transfer is None:
-                splitsum_resolve(gbuf, hit_pixels(face), pyr, lv, dif, piece)
+                splitsum_resolve(gbuf, pix, pyr, lv, dif, piece)
             else:
-                splitsum_resolve_occluded(scene, gbuf, face, hit_pixels(face), pyr, lv, dif, tr, sh, occlusion, piece)
+                splitsum_resolve_occluded(scene, gbuf, face, pix, pyr, lv, dif, tr, sh, occlusion, piece)
             out[i0:i0 + ni, y0:y0 + nr] = piece.reshape(ni, nr, w, 4)
     return out
 
@@ -742,7 +779,10 @@ def parse_args(argv=None):
     # only with --inner may --material be left out.  The exact spelling is enough: every shorter prefix (--inn, --inne) is also one of
     # --inner-material, which argparse refuses as ambiguous; abbreviations stay allowed, as the command without --inner always had them
     nested = any(a == '--inner' or a.startswith('--inner=') for a in args)
-    ap.add_argument('--material', type=str, required=not nested, help="directory with metallic.npy, roughness.npy, albedo.npy")
+    textured = any(a == '--texture' or a.startswith('--texture=') for a in args)
+    ap.add_argument('--material', type=str, required=not (nested or textured), help="directory with metallic.npy, roughness.npy, albedo.npy")
+    ap.add_argument('--texture', type=str, default=None,
+                    help="directory with atlas.npz of the mesh (bake_textures): materials from the texture atlas instead of per vertex")
     splitsum = any(a == '--splitsum' for a in args)
     ap.add_argument('--hdr', type=str, required=not splitsum, help="environment map: Radiance .hdr or .npy float [H,W,3]")
     ap.add_argument('--splitsum', action='store_true', default=False,
@@ -787,6 +827,8 @@ def parse_args(argv=None):
         ap.error("--transfer shadows the split-sum frame of the plain object: it needs --splitsum and excludes --inner")
     if flags.occlusion is not None and flags.transfer is None:
         ap.error("--occlusion needs --transfer")
+    if flags.texture is not None and flags.inner is not None:
+        ap.error("--texture holds the materials of the plain object: nested and thin-shell scenes (--inner) are not textured")
     if flags.splitsum:
         if flags.inner is not None:
             ap.error("--splitsum renders the plain object only: nested and thin-shell scenes (--inner) keep the Monte-Carlo path")
@@ -899,7 +941,11 @@ def main(argv=None):
     if flags.trans:
         V = (np.asarray(V, np.float64) @ TRANS.T).astype(np.float32)
     if flags.inner is None:
-        scene = Scene(V, F, load_materials(flags.material))
+        texture = None
+        if flags.texture is not None:
+            from .texture import load_textures
+            texture = load_textures(flags.texture, len(F))
+        scene = Scene(V, F, None if flags.material is None else load_materials(flags.material), texture=texture)
     else:
         Vi, Fi = M.read_ply(flags.inner)
         if flags.trans:
