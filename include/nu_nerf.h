@@ -1068,6 +1068,39 @@ int nu_rm_flip_claim(NU_RM_ARGS, float cos2_max, const int* npts, const long lon
 int nu_rm_flip_apply(NU_RM_ARGS, const int* win, int* F_io, hipStream_t stream);
 int nu_rm_relax(NU_RM_ARGS, float* Vout, hipStream_t stream);
 int nu_rm_project(const float* V, int nv, const unsigned char* vlock, const float* closest, float* Vout, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Quadric-error decimation to a face budget (csrc/decimate.hip; the driver nu_nerf_amd/decimate.py sorts and scans between the
+ * entries; Garland & Heckbert 1997 with memoryless quadrics, Lindstrom & Turk 1998).  One round on a compacted mesh and its
+ * remeshing tables (RM args above); float64 arithmetic, no float atomic, the same bits on every run.
+ *   nu_dm_quadrics   Q[nv,10] float64: per vertex the sum over its faces (corner order) of w (n^, d)(n^, d)^T, w = area; the unique
+ *                    entries (0,0) (0,1) (0,2) (0,3) (1,1) (1,2) (1,3) (2,2) (2,3) (3,3)
+ *   nu_dm_eval       per edge slot: cost[nh] float64, pos[nh,3] fp32 (the placement, rounded once) and npts[nh] int32 = 7 x rewritten
+ *                    faces of a collapse candidate; 0 (and zeros) for a slot that is no interior edge, has two locked ends, fails the
+ *                    link condition, has an opposite vertex of <= 3 faces, rewrites more than 32 faces, has a non-finite cost, or
+ *                    would leave a rewritten face with zero area, a normal turned by >= 90 degrees or a shape quality
+ *                    12 |n|^2 / (sum l^2)^2 below both min_quality2 and the face's old value
+ *   nu_dm_points     (surface bound) the candidates' query points (per rewritten face its 3 vertices, centroid, 3 edge midpoints) at
+ *                    3 poff[e] (int64 exclusive scan of npts) and lim (fp32, at poff[e]): the squared distance each may have,
+ *                    (max_dist - longest edge / sqrt(12))^2, which certifies every point of the face within max_dist; negative
+ *                    for a face too large to certify
+ *   nu_dm_keys       ckey[nh] u64 = ((bits(float32(cost + cost_floor)) >> 12) << 32) | mix32(e) for a candidate, INT64_MAX for
+ *                    the rest and, when pd2 (nu_lbvh_closest's squared distances of the points, +inf for a miss; NULL: no bound)
+ *                    exceeds lim at one of its points, for it too
+ *   nu_dm_claim      candidates with ckey <= threshold[0] (u64, on the device) atomicMin their key onto every vertex of every face
+ *                    of both ends (claim[nv] u64, reset here); win[nh] int32 = 1 where a candidate holds both ends and both opposite vertices
+ *   nu_dm_apply      winners in place (V_io, F_io may alias V, F): the kept vertex takes pos[e], the removed vertex's faces are
+ *                    rewritten, the edge's two faces become (-1,-1,-1)
+ * --------------------------------------------------------------------------------------------------------- */
+int nu_dm_quadrics(NU_RM_ARGS, double* Q, hipStream_t stream);
+int nu_dm_eval(NU_RM_ARGS, const double* Q, double min_quality2, double* cost, float* pos, int* npts, hipStream_t stream);
+int nu_dm_points(NU_RM_ARGS, const float* pos, const int* npts, const long long* poff, float max_dist, float* pts, float* lim,
+                 hipStream_t stream);
+int nu_dm_keys(const double* cost, const int* npts, const long long* poff, const float* pd2, const float* lim, int nh,
+               double cost_floor, unsigned long long* ckey, hipStream_t stream);
+int nu_dm_claim(NU_RM_ARGS, const unsigned long long* ckey, const unsigned long long* threshold, unsigned long long* claim, int* win,
+                hipStream_t stream);
+int nu_dm_apply(NU_RM_ARGS, const int* win, const float* pos, float* V_io, int* F_io, hipStream_t stream);
 #undef NU_RM_ARGS
 
 /* ---------------------------------------------------------------------------------------------------------

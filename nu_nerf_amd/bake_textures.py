@@ -1,4 +1,5 @@
 """python -m nu_nerf_amd.bake_textures --cfg CFG [--mesh PLY] [--ckpt PATH] [--size N] [--pad N] [--stage2 --which inner|outer] [--out DIR]
+[--decimate N]
 
 The materials of a trained model baked into a texture atlas instead of per vertex: the renderer named by the config
 loads data/model/{name}/model.pth as extract_materials does, every face of the mesh gets its own triangle of a SIZE x SIZE atlas
@@ -12,7 +13,9 @@ DIR gets
 
 --mesh defaults to data/meshes/{name}-{step}.ply, --out to data/materials/{name}-{step}/texture.  --size (default 2048) must give every
 face a cell of at least 5 + 3 PAD texels; --pad adds texels of margin around every triangle.  --stage2: a stage-2 config; --which inner
-(default) bakes the inner networks, outer the stage-1 networks the stage-2 model carries.
+(default) bakes the inner networks, outer the stage-1 networks the stage-2 model carries.  --decimate N: the mesh is first brought down
+to N faces (decimate.decimate), DIR also gets {mesh stem}_decimated.ply -- the mesh relight --texture DIR needs -- and the
+atlas and the exports are built on it, under that stem.
 """
 import argparse
 import os
@@ -29,7 +32,10 @@ def parse_args(argv=None):
     ap.add_argument('--stage2', action='store_true', help="the config is a stage-2 config")
     ap.add_argument('--which', choices=('inner', 'outer'), default=None, help="stage 2: the inner networks (default) or the stage-1 networks")
     ap.add_argument('--out', type=str, default=None, help="output directory (default data/materials/{name}-{step}/texture)")
+    ap.add_argument('--decimate', type=int, default=None, metavar='N', help="decimate the mesh to N faces before baking")
     flags = ap.parse_args(argv)
+    if flags.decimate is not None and flags.decimate < 4:
+        ap.error("--decimate must be >= 4")
     if flags.which is not None and not flags.stage2:
         ap.error("--which needs --stage2")
     if flags.size < 1:
@@ -83,6 +89,12 @@ def main(argv=None):
     print(f'successfully load {cfg["name"]} step {step}!')
     mesh_path, out, stem = output_paths(flags, cfg['name'], step)
     V, F = M.read_ply(mesh_path)
+    if flags.decimate is not None:
+        V, F = M.decimate(V, F, flags.decimate)
+        stem += '_decimated'
+        os.makedirs(out, exist_ok=True)
+        M.write_ply(os.path.join(out, stem + '.ply'), V, F)
+        print(f'wrote {os.path.join(out, stem + ".ply")}: {len(V)} vertices, {len(F)} triangles')
     try:
         T.atlas_layout(len(F), flags.size, flags.pad)
     except ValueError as e:

@@ -1,4 +1,5 @@
 """python -m nu_nerf_amd.extract_mesh --cfg CFG [--resolution 1024] [--ckpt PATH] [--out PATH] [--stage2] [--remesh] [--fix ...]
+[--decimate N]
 
 extract_mesh_stage1.py on the GPU: the renderer named by the config (`zero_thickness` picks the module set) loads
 data/model/{name}/model.pth (train_glue.save_checkpoint format), its SDF is sampled on the [-1,1]^3 grid (mesh.sdf_grid), marching
@@ -8,6 +9,8 @@ the reference's pymeshlab isotropic remeshing at 0.5 % of the bounding-box diago
 --fix also writes data/meshes/{name}-{step}_fixed.ply: the raw mesh without its floaters (components.remove_floaters; the switches
 of python -m nu_nerf_amd.clean_mesh: --keep, --min-area-frac, --min-faces, --drop-cavities, --connectivity), and --remesh then
 remeshes the fixed mesh instead of the raw one.  Without --fix every file is written as before.
+--decimate N also writes data/meshes/{name}-{step}_decimated.ply: the (fixed) mesh brought down to N faces by quadric-error collapses
+(decimate.decimate); it runs after --fix and before --remesh, which then starts from the decimated mesh.
 
 --stage2: extract_mesh_stage2.py -- a stage-2 checkpoint; the field is the inner sdf where the stage-1 sdf is < 0 and 1 elsewhere
 (mesh.stage2_inner_grid), no face flip.
@@ -27,9 +30,14 @@ def parse_args(argv=None):
     ap.add_argument('--remesh', action='store_true', help="also write the isotropically remeshed OUT_simplified.ply")
     ap.add_argument('--slab-points', type=int, default=None, help="grid points per SDF evaluation slab (default mesh.SLAB_POINTS)")
     ap.add_argument('--fix', action='store_true', help="also write OUT_fixed.ply without floaters; --remesh then starts from it")
+    ap.add_argument('--decimate', type=int, default=None, metavar='N',
+                    help="also write OUT_decimated.ply with about N faces (after --fix); --remesh then starts from it")
     from .clean_mesh import add_fix_options
     add_fix_options(ap)
-    return ap.parse_args(argv)
+    flags = ap.parse_args(argv)
+    if flags.decimate is not None and flags.decimate < 4:
+        ap.error("--decimate must be >= 4")
+    return flags
 
 
 def _renderer(cfg):
@@ -76,6 +84,12 @@ def main(argv=None):
         out_f = fixed_path(out)
         mesh.write_ply(out_f, V, F)
         print(f'wrote {out_f}: {len(V)} vertices, {len(F)} triangles')
+    if flags.decimate is not None:
+        from .decimate import decimated_path
+        V, F = mesh.decimate(V, F, flags.decimate)
+        out_d = decimated_path(out)
+        mesh.write_ply(out_d, V, F)
+        print(f'wrote {out_d}: {len(V)} vertices, {len(F)} triangles')
     if flags.remesh:
         from .remesh import remesh_isotropic, simplified_path
         Vs, Fs = remesh_isotropic(V, F)

@@ -11,6 +11,7 @@ run PyMCubes on a host grid: network/field.py:1286-1317).
   sample_surface    area-weighted deterministic surface samples on the device
   mesh_distance     Chamfer / Hausdorff distances of two meshes from surface samples and LBVH closest points
   remesh_isotropic  isotropic explicit remeshing (split / collapse / flip / relax on the device: remesh.py, csrc/remesh.hip)
+  decimate          quadric-error edge-collapse decimation to a face budget (decimate.py, csrc/decimate.hip)
   connected_components / component_stats / remove_floaters   component labelling, statistics and floater removal (components.py,
                     csrc/components.hip)
 
@@ -408,6 +409,13 @@ def remesh_isotropic(V, F, target_len=None, max_surf_dist=None, iterations=3, st
     """Isotropic explicit remeshing on the GPU (the reference's pymeshlab step before stage 2): see remesh.remesh_isotropic."""
     from .remesh import remesh_isotropic as _remesh
     return _remesh(V, F, target_len=target_len, max_surf_dist=max_surf_dist, iterations=iterations, stats=stats)
+
+
+def decimate(V, F, target_faces, max_surf_dist=None, min_quality=0.1, max_rounds=256, tolerance=0.02, stats=None):
+    """Quadric-error decimation to about target_faces faces on the GPU (never fewer): see decimate.decimate."""
+    from .decimate import decimate as _decimate
+    return _decimate(V, F, target_faces, max_surf_dist=max_surf_dist, min_quality=min_quality, max_rounds=max_rounds,
+                     tolerance=tolerance, stats=stats)
 
 
 def connected_components(V, F, connectivity='vertex', stats=None):

@@ -207,23 +207,23 @@ def thresholds(target_len, max_surf_dist):
             _f32(math.cos(math.radians(FLIP_MAX_NORMAL_ANGLE_DEG)) ** 2))
 
 
-def _validate(V, F):
+def _validate(V, F, who="remesh_isotropic"):
     from .lbvh import EmptyMeshError
     if V.dim() != 2 or V.shape[1] != 3 or F.dim() != 2 or F.shape[1] != 3:
-        raise ValueError(f"remesh_isotropic: V must be [Nv,3] and F [Nf,3], got {tuple(V.shape)} and {tuple(F.shape)}")
+        raise ValueError(f"{who}: V must be [Nv,3] and F [Nf,3], got {tuple(V.shape)} and {tuple(F.shape)}")
     if len(F) == 0 or len(V) == 0:
-        raise EmptyMeshError("remesh_isotropic: the mesh has no triangles")
+        raise EmptyMeshError(f"{who}: the mesh has no triangles")
     if 3 * len(F) >= 2 ** 31 or len(V) >= 2 ** 31:
-        raise ValueError("remesh_isotropic: the mesh is too large for int32 half-edge ids")
+        raise ValueError(f"{who}: the mesh is too large for int32 half-edge ids")
     bad = torch.stack([(F < 0).any() | (F >= len(V)).any(),
                        ((F[:, 0] == F[:, 1]) | (F[:, 1] == F[:, 2]) | (F[:, 2] == F[:, 0])).any(),
                        ~torch.isfinite(V).all()]).cpu().tolist()
     if bad[0]:
-        raise ValueError("remesh_isotropic: face index out of range")
+        raise ValueError(f"{who}: face index out of range")
     if bad[1]:
-        raise ValueError("remesh_isotropic: a face repeats a vertex")
+        raise ValueError(f"{who}: a face repeats a vertex")
     if bad[2]:
-        raise ValueError("remesh_isotropic: vertices must be finite")
+        raise ValueError(f"{who}: vertices must be finite")
 
 
 @torch.no_grad()
