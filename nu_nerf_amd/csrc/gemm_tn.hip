@@ -3,6 +3,7 @@
 //
 // Replaces the autograd weight / bias gradients of every `lin(x)` in network/field.py:133-150, :158-170, :265-289, :371-408.
 #include "gemm_epi.h"
+#include "wgrad_rm.h"
 
 // development aid: {shader cycles, 100 MHz wall ticks} of block 0 of the last mfma_peak launch
 __device__ unsigned long long nu_dbg_clk[2];
@@ -15,24 +16,8 @@ __device__ unsigned long long nu_dbg_clk[2];
 // inner loop is exactly the NT kernel's (one ds_read_b128 feeds four MFMA k-steps) and nothing consumes a global
 // load before the hand-over to LDS -- the loads stay in flight under the 64 MFMAs of the current chunk.
 // BIG = operands of 4 GiB or more (64-bit element offsets instead of one uniform base + a 32-bit byte offset).
-// Several weight-gradient problems in ONE launch: the (tile, split) blocks of problem i are the linear block ids
-// [blk0[i], blk0[i + 1]), tile fastest.  Each problem keeps its own operands, extents, split count and slab (NuGemmTN).
-#define NU_TN_BATCH_MAX 16
-struct NuGemmTNBatch {
-    NuGemmTN p[NU_TN_BATCH_MAX];
-    int blk0[NU_TN_BATCH_MAX + 1];
-    int n, pad_;
-};
-// which problem a block of a batched launch belongs to, and its (tile, split) there; `tiles` = output tiles of that problem
-static __device__ __forceinline__ int tn_batch_decode(const NuGemmTNBatch& b, int tile_edge, int& bx, int& split) {
-    int pi = 0;
-    for (int i = 1; i < b.n; ++i) pi = ((int)blockIdx.x >= b.blk0[i]) ? i : pi;
-    const int tiles = ((b.p[pi].N1 + tile_edge - 1) / tile_edge) * ((b.p[pi].N2 + tile_edge - 1) / tile_edge);
-    const int local = (int)blockIdx.x - b.blk0[pi];
-    split = local / tiles;
-    bx = local - split * tiles;
-    return pi;
-}
+// (NuGemmTNBatch and tn_batch_decode -- several weight-gradient problems in ONE launch -- live in wgrad_rm.h, shared with the
+// row-major kernels of wgrad_rm.hip)
 
 template <bool BIG, int PREC>
 static __device__ __forceinline__ void tn_body(const NuGemmTN& g, const int bx, const int split, const int grp) {
@@ -921,11 +906,14 @@ int nu_gemm_tn_launch(const NuGemmTN& g, hipStream_t stream) {
                                  ? (g.lda0 > g.ldb0 ? g.lda0 : g.ldb0) : (g.lda1 > g.ldb1 ? g.lda1 : g.ldb1);
     const bool big = (long long)g.P * max_ld * 4 >= (1LL << 32);
     if (prec == 0 && big_tile) {     // exact fp32: the pipelined kernel on 256 x 256 tiles where the shape allows, else gemm_tn_kernel
+        // 16-byte aligned operands below 4 GiB: the row-major stages of wgrad_rm.hip (same bits, a quarter of the load instructions)
+        if (!big && nu_wgrad_rm_ok(g) && (((uintptr_t)g.slab) & 15) == 0 && (g.sSlab & 3) == 0) return nu_wgrad_rm256_launch(g, stream);
         dim3 grid2((g.N1 / 256) * (g.N2 / 256), g.S, g.groups > 0 ? g.groups : 1);
         if (big) hipLaunchKernelGGL((gemm_tn2_kernel<true>), grid2, dim3(512), 0, stream, g);
         else hipLaunchKernelGGL((gemm_tn2_kernel<false>), grid2, dim3(512), 0, stream, g);
         return nu_launch_status();
     }
+    if (prec == 0 && !big && nu_wgrad_rm_ok(g) && (((uintptr_t)g.slab) & 15) == 0 && (g.sSlab & 3) == 0) return nu_wgrad_rm128_launch(g, stream);
     dim3 grid(nu_cdiv(g.N1, 128) * nu_cdiv(g.N2, 128), g.S, g.groups > 0 ? g.groups : 1), block(256);
     if (prec == 1) {
         // vector-load kernel: 16-byte aligned operands, rows of 8 or more elements (bf16 rows: a multiple of 8)
@@ -1193,7 +1181,8 @@ static inline bool tn_item_big(const NuGemmTN& g) {       // an operand of 4 GiB
     return (long long)g.P * (m0 > m1 ? m0 : m1) * 4 >= (1LL << 32);
 }
 
-// One launch of the items idx[0..m) (all of tile class `klass`: 1 = 128 x 128 tiles, 2 = 256 x 256), splits already chosen.
+// One launch of the items idx[0..m) (all of tile class `klass`: 1 = 128 x 128 tiles, 2 = 256 x 256; 3 / 4 = 256 x 256 / 128 x 128 with
+// row-major stages, wgrad_rm.hip), splits already chosen.
 static int wgrad_launch_batch(NuOpCtx* c, NuWgradItem* it, const int* idx, int m, int klass, hipStream_t stream) {
     long long bytes = 0;
     int ndesc = 0, nprob = 0;
@@ -1211,7 +1200,7 @@ static int wgrad_launch_batch(NuOpCtx* c, NuWgradItem* it, const int* idx, int m
     NuGemmTNBatch b;
     int np = 0, blocks = 0;
     double flops = 0, abytes = 0;
-    const int edge = klass == 2 ? 256 : 128;
+    const int edge = (klass == 2 || klass == 3) ? 256 : 128;
     for (int k = 0; k < m; ++k) {
         NuWgradItem& w = it[idx[k]];
         const NuGemmTN& g = w.g;
@@ -1240,9 +1229,13 @@ static int wgrad_launch_batch(NuOpCtx* c, NuWgradItem* it, const int* idx, int m
     b.blk0[np] = blocks;
     b.n = np; b.pad_ = 0;
     nu_ctx_ev_begin(c, stream);
-    if (klass == 2) hipLaunchKernelGGL((gemm_tn2b_kernel<false>), dim3(blocks), dim3(512), 0, stream, b);
-    else hipLaunchKernelGGL((gemm_tnb_kernel<false>), dim3(blocks), dim3(256), 0, stream, b);
-    rc = nu_launch_status();
+    if (klass >= 3) {
+        rc = klass == 3 ? nu_wgrad_rm256_launch_batch(b, blocks, stream) : nu_wgrad_rm128_launch_batch(b, blocks, stream);
+    } else {
+        if (klass == 2) hipLaunchKernelGGL((gemm_tn2b_kernel<false>), dim3(blocks), dim3(512), 0, stream, b);
+        else hipLaunchKernelGGL((gemm_tnb_kernel<false>), dim3(blocks), dim3(256), 0, stream, b);
+        rc = nu_launch_status();
+    }
     nu_ctx_ev_end(c, stream, 1.0, flops, abytes);
     return rc;
 }
@@ -1303,10 +1296,14 @@ extern "C" int nu_wgrad_flush(NuOpCtx* c, hipStream_t stream) {
     // scalar transposing loads, which more waves hide: a grid of 1024 measured 121.4 TFLOP/s over a step's weight gradients against
     // 118.0 at 512 (same box, alternating; 512 rays: 7.61 vs 7.74 ms/step)
     plan(1, 128, 1024);
+    // the items whose operands are 16-byte aligned take the row-major kernels, 3 = 256 x 256 tiles, 4 = 128 x 128 (the arena's slabs are 256-byte aligned); the
+    // splits above do not depend on it, so an item has the same bits on either path
+    for (int i = 0; i < n; ++i)
+        if (klass[i] >= 1 && nu_wgrad_rm_ok(it[i].g)) klass[i] = klass[i] == 2 ? 3 : 4;
     // ---- launch: singles first, then one launch per class (more when the batch table or the arena cannot take a class at once) ----
     for (int i = 0; i < n; ++i)
         if (klass[i] == 0) { const int rc = wgrad_launch_single(c, it[i], stream); if (rc != NU_OK) return rc; }
-    for (int k = 2; k >= 1; --k) {
+    for (int k = 4; k >= 1; --k) {
         int idx[NU_WGRAD_QUEUE_MAX], m = 0, nprob = 0;
         long long bytes = 0;
         for (int i = 0; i <= n; ++i) {
