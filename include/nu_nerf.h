@@ -512,7 +512,7 @@ int nu_relight_splitsum_occluded(const float* gbuf, const int* face, const int* 
  *                      either; zero on unowned texels.  A texel's bits do not depend on y0 / rows.
  *   nu_atlas_sample    out [n, 5] = the bilinear lookup at barycentrics uv [n, 2] = (u, v) (weights of vertices 1 and 2) of face [n];
  *                      a face outside [0, n_faces) gives zeros.  atlas = two planes [2, T, T, 4]: (albedo r, g, b, metallic), then
- *                      (roughness, three spare lanes); out = albedo, metallic, roughness.  u = clamp(u, 0, 1), v = clamp(v, 0, 1 - u),
+ *                      (roughness, then the texel's object-space normal x, y, z or three zeros); out = albedo, metallic, roughness.  u = clamp(u, 0, 1), v = clamp(v, 0, 1 - u),
  *                      s = pad + u L, t = min(pad + v L, (2 pad + L) - s), taps floor(s), floor(s) + 1, floor(t), floor(t) + 1 in the
  *                      face's frame, fractions fs, ft; value = lo + ft (hi - lo), lo = t00 + fs (t10 - t00), hi = t01 + fs (t11 - t01),
  *                      where fs == 0 (ft == 0) leaves the +1 taps out altogether.  Every tap that takes part has s + t <= c - 2 - pad:
@@ -521,7 +521,15 @@ int nu_relight_splitsum_occluded(const float* gbuf, const int* face, const int* 
  *                      whose face id is in [0, n_faces): (u, v) of the stored hit point in its face by the formula of
  *                      nu_relight_splitsum_occluded above, nu_atlas_sample's lookup, and columns 10..14 of the row (albedo, metallic,
  *                      roughness) are OVERWRITTEN.  Every other column, every unlisted row and listed miss rows stay as they are.
- *   NU_ERR_ARG (all three): n_faces < 1, size < 1 or > NU_ATLAS_MAX_SIZE, pad < 0 or > NU_ATLAS_MAX_PAD, L < 2, n_verts < 1, a negative
+ *   nu_atlas_sample_normal   out [n, 3] = nu_atlas_sample's lookup (taps, fractions, the fs == 0 / ft == 0 rule, the mix expression, the
+ *                      clamp into the triangle) on lanes y, z, w of plane 1 -- the object-space normal of the texel (DESIGN.md section
+ *                      32), zero in a texture without normals -- divided by its length sqrt((x x + y y) + z z); zero when that length
+ *                      is not in (0, 1e30), and for a face outside [0, n_faces).
+ *   nu_atlas_gbuffer_normal  per listed row as nu_atlas_gbuffer: (u, v) of the stored hit point, the lookup of nu_atlas_sample_normal; a
+ *                      mix without a length in (0, 1e30) leaves the row as it is, otherwise columns 7..9 (the shading normal) are
+ *                      OVERWRITTEN with ns = mix / length, negated when ns . ng < 0, ng = columns 4..6 (the viewer-facing geometric
+ *                      normal): the rule of the G-buffer pass for vertex normals.  Nothing else is written.
+ *   NU_ERR_ARG (all five): n_faces < 1, size < 1 or > NU_ATLAS_MAX_SIZE, pad < 0 or > NU_ATLAS_MAX_PAD, L < 2, n_verts < 1, a negative
  *   count, rows outside the atlas, a NULL array that is read or written, vnormals without normal or the reverse.  A count of 0
  *   launches nothing.
  * --------------------------------------------------------------------------------------------------------- */
@@ -534,6 +542,10 @@ int nu_atlas_sample(const float* atlas, int size, int n_faces, int pad, const in
                     hipStream_t stream);
 int nu_atlas_gbuffer(float* gbuf, const int* face, const int* pix, int n_pix, const float* V, int n_verts, const int* F, int n_faces,
                      const float* atlas, int size, int pad, hipStream_t stream);
+int nu_atlas_sample_normal(const float* atlas, int size, int n_faces, int pad, const int* face, const float* uv, int n, float* out,
+                           hipStream_t stream);
+int nu_atlas_gbuffer_normal(float* gbuf, const int* face, const int* pix, int n_pix, const float* V, int n_verts, const int* F, int n_faces,
+                            const float* atlas, int size, int pad, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Relighting of the NESTED object (the project's own transport, pinned against no other renderer): a
@@ -754,6 +766,14 @@ int nu_sdf_fused16_fwd(const NuSdfNet* net, const float* X, int x_ld, int P, flo
  *   NU_ERR_ARG: net or X NULL, P < 0, x_ld < 3.  P == 0 launches nothing. */
 int nu_sdf_jet_fwd(const NuSdfNet* net, const float* X, int x_ld, int P, float* sdf, float* grad, float* hess, float* mean,
                    float* gauss, float* normal, hipStream_t stream);
+/* The FIRST-order jet of the SDF as ONE fully-fused no-gradient kernel (csrc/sdf_grad.hip): value, gradient and unit
+ * normal, four rows per point (value, d/dx, d/dy, d/dz) through the pipeline of nu_sdf_jet_fwd, 16 points on all 64 rows of a tile where
+ * the second-order jet has 6 on 60.  The bulk tool of the normal-map bake; exact fp32 on the fp32 packed tables in every mlp_dtype.
+ *   X [P, x_ld] (x = the first three floats of a row, x_ld >= 3); sdf [P] (the bits of nu_sdf_fused_fwd), grad [P,3] and normal [P,3] =
+ *   grad / |grad| (the bits of nu_sdf_jet_fwd; normal = 0 where |grad|^2 < 1e-12).  Every output pointer may be NULL.  No workspace.
+ *   A point's outputs do not depend on P, on its position in X or on its neighbours.
+ *   NU_ERR_ARG: net or X NULL, P < 0, x_ld < 3.  P == 0 launches nothing. */
+int nu_sdf_grad_fwd(const NuSdfNet* net, const float* X, int x_ld, int P, float* sdf, float* grad, float* normal, hipStream_t stream);
 /* Sphere tracing of the SDF as ONE fully-fused no-gradient kernel (csrc/sdf_trace.hip; network/tracing.py:103-164 called on each ray
  * alone): persistent workgroups hold 64 ray slots in LDS, run the pipeline of nu_sdf_fused_fwd on the slot positions, apply the step
  * behind the head and refill finished slots from a statically assigned ray sequence.  Per ray, every operation a separately rounded

@@ -1,5 +1,5 @@
 """python -m nu_nerf_amd.bake_textures --cfg CFG [--mesh PLY] [--ckpt PATH] [--size N] [--pad N] [--stage2 --which inner|outer] [--out DIR]
-[--decimate N]
+[--decimate N] [--normals sdf]
 
 The materials of a trained model baked into a texture atlas instead of per vertex: the renderer named by the config
 loads data/model/{name}/model.pth as extract_materials does, every face of the mesh gets its own triangle of a SIZE x SIZE atlas
@@ -15,7 +15,10 @@ DIR gets
 face a cell of at least 5 + 3 PAD texels; --pad adds texels of margin around every triangle.  --stage2: a stage-2 config; --which inner
 (default) bakes the inner networks, outer the stage-1 networks the stage-2 model carries.  --decimate N: the mesh is first brought down
 to N faces (decimate.decimate), DIR also gets {mesh stem}_decimated.ply -- the mesh relight --texture DIR needs -- and the
-atlas and the exports are built on it, under that stem.
+atlas and the exports are built on it, under that stem.  --normals sdf: the SDF's unit normal at every owned texel is
+baked as well (one more fused kernel per pass): atlas.npz gains normal [T,T,3] (object space; relight --texture DIR --normal-map shades
+with it), DIR gets normal.png (tangent space, per-face flat frames) and the glTF names it as normalTexture with NORMAL / TANGENT to
+match; the JSON line printed at the end counts the texels whose normal faces away from their face (normal_backfacing).  The OBJ is unchanged.
 """
 import argparse
 import os
@@ -33,6 +36,7 @@ def parse_args(argv=None):
     ap.add_argument('--which', choices=('inner', 'outer'), default=None, help="stage 2: the inner networks (default) or the stage-1 networks")
     ap.add_argument('--out', type=str, default=None, help="output directory (default data/materials/{name}-{step}/texture)")
     ap.add_argument('--decimate', type=int, default=None, metavar='N', help="decimate the mesh to N faces before baking")
+    ap.add_argument('--normals', choices=('sdf',), default=None, help="also bake a normal map: sdf = the SDF network's normal at every texel")
     flags = ap.parse_args(argv)
     if flags.decimate is not None and flags.decimate < 4:
         ap.error("--decimate must be >= 4")
@@ -99,14 +103,19 @@ def main(argv=None):
         T.atlas_layout(len(F), flags.size, flags.pad)
     except ValueError as e:
         raise SystemExit(str(e))
-    atlas = T.bake_textures(network, V, F, size=flags.size, pad=flags.pad, which=which_of(flags))
+    atlas = T.bake_textures(network, V, F, size=flags.size, pad=flags.pad, which=which_of(flags), normals=flags.normals)
     T.write_textures(out, atlas)
     normals = vertex_normals_and_curvature(torch.from_numpy(V), torch.from_numpy(F).long())[0].numpy()
     T.write_obj(os.path.join(out, stem + '.obj'), V, F, atlas['uv'], normals, out)
-    T.write_gltf(os.path.join(out, stem + '.gltf'), V, F, atlas['uv'], normals, out)
+    T.write_gltf(os.path.join(out, stem + '.gltf'), V, F, atlas['uv'], normals, out, normal_map=atlas if flags.normals else None)
     owned = int((atlas['face'] >= 0).sum())
     print(f'wrote {out}/atlas.npz, albedo.png, orm.png, {stem}.obj, {stem}.mtl, {stem}.gltf, {stem}.bin: {len(F)} faces of {mesh_path} in '
           f'{flags.size} x {flags.size} texels, {owned} owned ({100.0 * owned / flags.size ** 2:.1f} %)')
+    if flags.normals:
+        import json
+        backfacing = T.tangent_normal_image(atlas, V, F, count=True)[1]
+        print(json.dumps({'normals': flags.normals, 'normal_png': os.path.join(out, 'normal.png'), 'owned_texels': owned,
+                          'normal_backfacing': backfacing}))
     return out
 
 

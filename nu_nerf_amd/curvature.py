@@ -49,6 +49,25 @@ def bake_curvature(renderer, points, *, which=None, hessian=False):
     return out
 
 
+@torch.no_grad()
+def bake_normals(renderer, points, *, which=None):
+    """Value, gradient and unit normal of the SDF at `points` ([V, >= 3] float32 device tensor, contiguous) -> dict of device tensors
+    'sdf' [V], 'gradient' [V,3], 'normal' [V,3] = gradient / |gradient| (it points where f grows; 0 where |gradient|^2 < 1e-12): the
+    three bake_curvature returns under these names, bit for bit, from ONE launch of the first-order kernel (csrc/sdf_grad.hip,
+    nu_sdf_grad_fwd) for any V -- four rows per point instead of ten, the tool for the texels of an atlas (texture.bake_textures(...,
+    normals='sdf')).  which: see materials.bake_engine."""
+    eng = bake_engine(renderer, which)
+    points = _check_points(points, eng.dev)
+    V = points.shape[0]
+    e = lambda *s: torch.empty(*s, dtype=torch.float32, device=eng.dev)      # noqa: E731
+    out = {'sdf': e(V), 'gradient': e(V, 3), 'normal': e(V, 3)}
+    if V == 0:
+        return out
+    eng.pack()
+    eng.sdf_grad(points.data_ptr(), points.shape[1], V, out['sdf'], out['gradient'], out['normal'])
+    return out
+
+
 def predict_curvature(renderer, mesh=None, which=None):
     """{'gaussian' [V,1], 'mean' [V], 'normal' [V,3]} as float32 numpy arrays in the vertex order of the mesh (materials.mesh_vertices:
     None = data/meshes/{name}-300000.ply, a PLY path, or a (V, F) pair)."""

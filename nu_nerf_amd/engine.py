@@ -746,6 +746,14 @@ class Stage1Engine:
         self.lib.nu_sdf_jet_fwd(ctypes.byref(self._sdf_net), X, x_ld, P, addr(sdf), addr(grad), addr(hess), addr(mean), addr(gauss),
                                 addr(normal), self.stream())
 
+    def sdf_grad(self, X, x_ld, P, sdf=None, grad=None, normal=None):
+        """Value, gradient and unit normal grad / |grad| of the SDF network at P points (X as in sdf_jet) in ONE no-gradient kernel
+        (csrc/sdf_grad.hip: the first-order jet, four rows per point, 16 points a tile), written to the fp32 tensors given (sdf [P]; grad,
+        normal [P,3]; None: not written) -- the bits sdf_jet writes for the same three.  No workspace; reads the fp32 packed tables."""
+        if self._desc_dev is None or self._ptr_sig != self._signature():
+            self._upload_descs()
+        self.lib.nu_sdf_grad_fwd(ctypes.byref(self._sdf_net), X, x_ld, P, addr(sdf), addr(grad), addr(normal), self.stream())
+
     # ------------------------------------------------------------------ SDF sphere tracing
     def sdf_trace(self, O, o_ld, D, d_ld, R, *, fg=None, max_iter=200, threshold=1e-5, bound_radius=1.0, flags=0, pos=None, t=None,
                   sdf=None, iters=None, hit=None):

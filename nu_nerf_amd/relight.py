@@ -1,4 +1,4 @@
-"""python -m nu_nerf_amd.relight --mesh PLY --material DIR --hdr FILE --name NAME [--texture DIR] [--trans] [--num 360 --width 800 --height 800
+"""python -m nu_nerf_amd.relight --mesh PLY --material DIR --hdr FILE --name NAME [--texture DIR [--normal-map]] [--trans] [--num 360 --width 800 --height 800
 --samples 1024 --cam_dist 3.0 --azimuth 0 --elevation 45] [--splitsum [--pyramid DIR | --levels R ...] [--transfer DIR [--occlusion ao|sh]]] [--inner PLY --inner-material DIR (--ior VALUE_OR_DIR | --shell DIR_OR_PAIR [--shell-curvature FILE])]
 
 relight.py + blender_backend/relight_backend.py on the GPU: the extracted mesh, the per-vertex DIR/metallic.npy, roughness.npy and
@@ -18,7 +18,9 @@ extract_materials --stage2 wrote for such a config, or "IOR,THICKNESS" (two numb
 
 --texture DIR: the atlas.npz `python -m nu_nerf_amd.bake_textures` wrote for this mesh: albedo, metallic and roughness of
 every hit come from the texture atlas, looked up at the hit point, instead of the per-vertex arrays (--material is then not needed).  Works
-in the Monte-Carlo and the --splitsum path, also with --transfer; not with --inner.
+in the Monte-Carlo and the --splitsum path, also with --transfer; not with --inner.  --normal-map (with --texture): the shading normal
+of every hit comes from the atlas as well -- the SDF normals `bake_textures --normals sdf` put there -- instead of the mix
+of the mesh's vertex normals; a directory whose atlas.npz has no normals is refused.
 
 --hdr takes a Radiance .hdr (RGBE, flat or run-length scanlines) or a .npy float [H,W,3]; the map is z up in the mesh's frame.
 --focal_mm / --sensor_mm: Blender's default camera (50 mm on a 36 mm sensor fitted to the larger image side).  --seed, --chunk
@@ -282,20 +284,26 @@ def _packed_texture(scene, texture):
     return atlas
 
 
-def _texture_of(scene, texture):
-    """texture= of a relight call: the argument if given, otherwise the Scene's own atlas (None: per-vertex materials)."""
-    return scene.texture if texture is None else _packed_texture(scene, texture)
+def _texture_of(scene, texture, normal_map=False):
+    """texture= of a relight call: the argument if given, otherwise the Scene's own atlas (None: per-vertex materials).  normal_map
+    asks for an atlas that carries normals: ValueError without one."""
+    tex = scene.texture if texture is None else _packed_texture(scene, texture)
+    if normal_map and (tex is None or not tex.has_normal):
+        raise ValueError("normal_map=True needs a texture with normals (texture.bake_textures(..., normals='sdf'))")
+    return tex
 
 
 def relight_linear(V, F, materials, env, poses, h, w, samples, seed=0, chunk=256, rows=None, images=1, K=None, img0=0,
-                   eps=ORIGIN_EPS, texture=None):
+                   eps=ORIGIN_EPS, texture=None, normal_map=False):
     """Linear radiance float32 [n,h,w,4] (RGB, alpha 1 on hit pixels and 0 elsewhere) on the device.  poses [n,3,4]: world -> camera in
     the mesh's frame (camera_in_mesh_frame of relighting_poses); K: [3,3] (default intrinsics(h, w)); env [H,W,3]; V may be a Scene.
     Image i is sampled as image img0 + i.  Work is done `images` images x `rows` image rows x `chunk` samples at a time; the result
     does not depend on any of the three, bit for bit.  Device memory besides the mesh, the environment and the result: 100 bytes per
     pixel of a piece (G-buffer row, face id, hit list) plus at most VIS_BYTES of visibility bytes -- independent of `samples`.
     texture: a texture atlas of the mesh (default: the Scene's own, if it has one) -- the material columns of every hit
-    row are then looked up in it at the hit point (texture.texture_gbuffer) before anything is shaded; None without one: untouched."""
+    row are then looked up in it at the hit point (texture.texture_gbuffer) before anything is shaded; None without one: untouched.
+    normal_map=True: the shading normal of every hit row is taken from the texture's normal lanes as well (it needs a
+    texture baked with normals='sdf'); the visibility and resolve kernels run unchanged on that G-buffer."""
     import torch
     from .mask_render import _cams
     samples, chunk = int(samples), int(chunk)
@@ -305,7 +313,7 @@ def relight_linear(V, F, materials, env, poses, h, w, samples, seed=0, chunk=256
         raise ValueError("chunk, rows and images must be >= 1")
     scene = _scene(V, F, materials)
     dev = scene.device
-    tex = _texture_of(scene, texture)
+    tex = _texture_of(scene, texture, normal_map)
     poses = np.asarray(poses.cpu() if torch.is_tensor(poses) else poses, np.float64).reshape(-1, 3, 4)
     K = intrinsics(h, w) if K is None else np.asarray(K, np.float64)
     cams = _cams(K.astype(np.float32), poses.astype(np.float32), dev)
@@ -320,7 +328,7 @@ def relight_linear(V, F, materials, env, poses, h, w, samples, seed=0, chunk=256
             pix_all = hit_pixels(face)
             if tex is not None:
                 from .texture import texture_gbuffer
-                texture_gbuffer(scene, face, gbuf, pix_all, tex)
+                texture_gbuffer(scene, face, gbuf, pix_all, tex, normals=bool(normal_map))
             piece = torch.zeros(ni * nr * w, 4, dtype=torch.float32, device=dev)
             per = max(1, min(VIS_BYTES // min(chunk, samples), (2 ** 31 - 1) // ((min(chunk, samples) + 15) // 16)))
             for p0 in range(0, int(pix_all.shape[0]), per):
@@ -444,7 +452,7 @@ def _transfer_args(scene, transfer, occlusion, env_sh):
 
 
 def relight_splitsum_linear(V, F, materials, pyramid, levels, diffuse, poses, h, w, rows=None, images=1, K=None, transfer=None,
-                            occlusion='ao', env_sh=None, texture=None):
+                            occlusion='ao', env_sh=None, texture=None, normal_map=False):
     """Linear radiance float32 [n,h,w,4] (alpha 1 on hit pixels, 0 elsewhere) of the split-sum model the networks were trained under:
     (1 - metallic) albedo Ld(n) + (F0 A + B) L(reflect(v, n), roughness), L from the prefiltered `pyramid` [L,ph,pw,3] at the roughness
     `levels` [L], Ld from `diffuse` [dh,dw,3], (A, B) from the shipped table.  No sampling, no visibility, no interreflection: a frame is
@@ -453,7 +461,8 @@ def relight_splitsum_linear(V, F, materials, pyramid, levels, diffuse, poses, h,
     transfer: float32 [Nv,16] rows of transfer.bake_transfer for the mesh's vertices -- the frame then has contact shadows and
     self-occlusion: occlusion='ao' darkens the diffuse term by the ambient occlusion, 'sh' lights it with the transfer
     vector against env_sh [9,3] (environment.project_sh of the environment); None is the unshadowed path above, untouched.
-    texture: as relight_linear's -- the hit rows take albedo, metallic and roughness from the atlas before the resolve (either one)."""
+    texture: as relight_linear's -- the hit rows take albedo, metallic and roughness from the atlas before the resolve (either one).
+    normal_map: as relight_linear's; with transfer= the baked per-vertex transfer rows are used as they are."""
     import torch
     from .mask_render import _cams
     if images < 1 or (rows is not None and rows < 1):
@@ -463,7 +472,7 @@ def relight_splitsum_linear(V, F, materials, pyramid, levels, diffuse, poses, h,
     pyr, lv = pack_pyramid(pyramid, levels)
     pyr, dif = torch.from_numpy(pyr).to(dev), torch.from_numpy(pack_env(diffuse)).to(dev)
     tr, sh = (None, None) if transfer is None else _transfer_args(scene, transfer, occlusion, env_sh)
-    tex = _texture_of(scene, texture)
+    tex = _texture_of(scene, texture, normal_map)
     poses = np.asarray(poses.cpu() if torch.is_tensor(poses) else poses, np.float64).reshape(-1, 3, 4)
     K = intrinsics(h, w) if K is None else np.asarray(K, np.float64)
     cams = _cams(K.astype(np.float32), poses.astype(np.float32), dev)
@@ -478,7 +487,7 @@ def relight_splitsum_linear(V, F, materials, pyramid, levels, diffuse, poses, h,
             pix = hit_pixels(face)
             if tex is not None:
                 from .texture import texture_gbuffer
-                texture_gbuffer(scene, face, gbuf, pix, tex)
+                texture_gbuffer(scene, face, gbuf, pix, tex, normals=bool(normal_map))
             if transfer is None:
                 splitsum_resolve(gbuf, pix, pyr, lv, dif, piece)
             else:
@@ -783,6 +792,8 @@ def parse_args(argv=None):
     ap.add_argument('--material', type=str, required=not (nested or textured), help="directory with metallic.npy, roughness.npy, albedo.npy")
     ap.add_argument('--texture', type=str, default=None,
                     help="directory with atlas.npz of the mesh (bake_textures): materials from the texture atlas instead of per vertex")
+    ap.add_argument('--normal-map', dest='normal_map', action='store_true', default=False,
+                    help="with --texture: shade with the normals baked into the atlas (bake_textures --normals sdf) instead of the vertex normals")
     splitsum = any(a == '--splitsum' for a in args)
     ap.add_argument('--hdr', type=str, required=not splitsum, help="environment map: Radiance .hdr or .npy float [H,W,3]")
     ap.add_argument('--splitsum', action='store_true', default=False,
@@ -829,6 +840,14 @@ def parse_args(argv=None):
         ap.error("--occlusion needs --transfer")
     if flags.texture is not None and flags.inner is not None:
         ap.error("--texture holds the materials of the plain object: nested and thin-shell scenes (--inner) are not textured")
+    if flags.normal_map:
+        if flags.texture is None:
+            ap.error("--normal-map needs --texture: the normals are in the atlas")
+        path = os.path.join(flags.texture, 'atlas.npz')
+        if os.path.exists(path):                               # a missing file is load_textures' error, as without --normal-map
+            with np.load(path) as z:
+                if 'normal' not in z.files:
+                    ap.error(f"--normal-map: {path} has no normals (bake_textures --normals sdf writes them)")
     if flags.splitsum:
         if flags.inner is not None:
             ap.error("--splitsum renders the plain object only: nested and thin-shell scenes (--inner) keep the Monte-Carlo path")
@@ -981,9 +1000,11 @@ def main(argv=None):
     K = intrinsics(flags.height, flags.width, flags.focal_mm, flags.sensor_mm)
     for k in todo:
         if flags.splitsum:
-            img = relight_splitsum(scene, None, None, pyramid, levels, diffuse, poses[k:k + 1], flags.height, flags.width, K=K, **kw)
+            img = relight_splitsum(scene, None, None, pyramid, levels, diffuse, poses[k:k + 1], flags.height, flags.width, K=K,
+                                   normal_map=flags.normal_map, **kw)
         elif flags.inner is None:
-            img = relight(scene, None, None, env, poses[k:k + 1], flags.height, flags.width, flags.samples, flags.seed, flags.chunk, K=K, img0=k)
+            img = relight(scene, None, None, env, poses[k:k + 1], flags.height, flags.width, flags.samples, flags.seed, flags.chunk, K=K, img0=k,
+                          normal_map=flags.normal_map)
         else:
             img = relight_nested(scene, env, poses[k:k + 1], flags.height, flags.width, flags.samples, flags.seed, flags.chunk, K=K, img0=k)
         write_png(frame_path(out, k), img[0])

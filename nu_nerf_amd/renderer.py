@@ -332,12 +332,12 @@ class NeROShapeRenderer(nn.Module):
         from .materials import predict_materials
         return predict_materials(self, mesh)
 
-    def predict_textures(self, mesh=None, size=2048, which=None):
+    def predict_textures(self, mesh=None, size=2048, which=None, normals=None):
         """The same materials baked into a per-triangle texture atlas of `size` texels a side (texture.py): {'albedo' [T,T,3],
         'metallic' [T,T], 'roughness' [T,T], 'face' [T,T], 'uv' [Nf,3,2], 'layout'} as numpy arrays, for `mesh` as predict_materials
-        reads it."""
+        reads it.  normals='sdf' adds 'normal' [T,T,3], the SDF's unit normal at every texel."""
         from .texture import predict_textures
-        return predict_textures(self, mesh, size, which)
+        return predict_textures(self, mesh, size, which, normals=normals)
 
     def predict_curvature(self, mesh=None):
         """{'gaussian' [V,1], 'mean' [V], 'normal' [V,3]} (float32 numpy) of the SDF's zero set at the vertices of `mesh` (as

@@ -212,10 +212,11 @@ class Stage2Renderer(nn.Module):
         from .materials import predict_materials
         return predict_materials(self, mesh, which)
 
-    def predict_textures(self, mesh=None, size=2048, which='inner'):
-        """predict_materials baked into a per-triangle texture atlas of `size` texels a side (texture.py), `which` as there."""
+    def predict_textures(self, mesh=None, size=2048, which='inner', normals=None):
+        """predict_materials baked into a per-triangle texture atlas of `size` texels a side (texture.py), `which` as there;
+        normals='sdf' adds the SDF normal of every texel."""
         from .texture import predict_textures
-        return predict_textures(self, mesh, size, which)
+        return predict_textures(self, mesh, size, which, normals=normals)
 
     def predict_curvature(self, mesh=None, which='inner'):
         """Curvature of an SDF of the model at the vertices of `mesh` (curvature.py): which='inner' sdf_network_inner, which='outer' the

@@ -6,6 +6,9 @@ order (atlas_layout).  A texel holds the material at EXTRAPOLATED barycentrics o
 texels it owns and a bilinear lookup anywhere in its triangle -- corners and edges included -- reads only texels of that face.
 csrc/texture.hip has the three kernels: nu_atlas_texels (texel -> surface point), nu_atlas_sample (the lookup) and nu_atlas_gbuffer
 (lookup at the hit points of a G-buffer, into its material columns); materials.bake_materials evaluates the networks at the texel points.
+Opt-in: normals='sdf' also bakes the SDF's unit normal at every texel (curvature.bake_normals) into the spare lanes of the
+atlas; nu_atlas_sample_normal / nu_atlas_gbuffer_normal look it up, relight takes it as the shading normal (normal_map=True), and
+write_gltf exports it as a tangent-space normalTexture in per-face flat frames.
 
     atlas = bake_textures(renderer, V, F, size=2048)            # device tensors + layout
     write_textures(directory, atlas)                             # atlas.npz, albedo.png, orm.png
@@ -119,14 +122,24 @@ def atlas_texels(V, F, layout, vnormals=None, y0=0, rows=None):
     return texel[..., :3], texel.view(torch.int32)[..., 3], (None if normal is None else normal[..., :3])
 
 
-def bake_textures(renderer, V, F, size=2048, pad=0, which=None, rows_per_pass=None):
+def _normals_arg(normals):
+    if normals not in (None, 'sdf'):
+        raise ValueError(f"normals must be None or 'sdf', got {normals!r}")
+    return normals is not None
+
+
+def bake_textures(renderer, V, F, size=2048, pad=0, which=None, rows_per_pass=None, normals=None):
     """The material networks of `renderer` baked into an atlas of `size` texels a side for the mesh (V, F): dict of device tensors
     'albedo' [T,T,3], 'metallic' [T,T], 'roughness' [T,T] (float32, 0 where no face owns the texel), 'face' [T,T] int32 (-1 where
     unowned), plus 'uv' float32 numpy [Nf,3,2] (atlas_uv) and 'layout'.  Texel points come from nu_atlas_texels in passes of
     `rows_per_pass` rows (default: PASS_TEXELS texels), the owned ones are selected (one host read per pass, the count) and evaluated
-    by materials.bake_materials -- the fused bake kernel, `which` as there; the result does not depend on rows_per_pass, bit for bit."""
+    by materials.bake_materials -- the fused bake kernel, `which` as there; the result does not depend on rows_per_pass, bit for bit.
+    normals='sdf' adds 'normal' float32 [T,T,3]: the SDF's unit normal grad f / |grad f| at the same selected texel
+    points (curvature.bake_normals, one more launch per pass), zero where unowned.  It is the raw object-space normal -- it points
+    where f grows; nothing is flipped here -- and every other key is what normals=None returns."""
     import torch
     from .materials import bake_engine, bake_materials
+    want_normals = _normals_arg(normals)
     V, F = _mesh_on_device(V, F, bake_engine(renderer, which).dev)
     lay = atlas_layout(int(F.shape[0]), size, pad)
     T = lay['size']
@@ -136,6 +149,7 @@ def bake_textures(renderer, V, F, size=2048, pad=0, which=None, rows_per_pass=No
     dev = V.device
     five = torch.zeros(T * T, CH, dtype=torch.float32, device=dev)
     face = torch.empty(T, T, dtype=torch.int32, device=dev)
+    normal = torch.zeros(T * T, 3, dtype=torch.float32, device=dev) if want_normals else None
     for y0 in range(0, T, rows_per_pass):
         nr = min(rows_per_pass, T - y0)
         points, ids, _ = atlas_texels(V, F, lay, y0=y0, rows=nr)
@@ -143,32 +157,43 @@ def bake_textures(renderer, V, F, size=2048, pad=0, which=None, rows_per_pass=No
         sel = (ids.reshape(-1) >= 0).nonzero().flatten()
         if sel.numel() == 0:
             continue
-        out = bake_materials(renderer, points.reshape(-1, 3)[sel].contiguous(), which=which)
+        owned = points.reshape(-1, 3)[sel].contiguous()
+        out = bake_materials(renderer, owned, which=which)
         five[y0 * T + sel] = torch.cat([out['albedo'], out['metallic'], out['roughness']], 1)
+        if want_normals:
+            from .curvature import bake_normals
+            normal[y0 * T + sel] = bake_normals(renderer, owned, which=which)['normal']
     five = five.reshape(T, T, CH)
-    return {'albedo': five[..., 0:3].contiguous(), 'metallic': five[..., 3].contiguous(), 'roughness': five[..., 4].contiguous(),
-            'face': face, 'uv': atlas_uv(lay), 'layout': lay}
+    atlas = {'albedo': five[..., 0:3].contiguous(), 'metallic': five[..., 3].contiguous(), 'roughness': five[..., 4].contiguous(),
+             'face': face, 'uv': atlas_uv(lay), 'layout': lay}
+    if want_normals:
+        atlas['normal'] = normal.reshape(T, T, 3)
+    return atlas
 
 
 class PackedAtlas:
-    """The device texture of the two lookup kernels: tex float32 [2,T,T,4] = (albedo rgb, metallic), (roughness, 0, 0, 0), + layout."""
+    """The device texture of the lookup kernels: tex float32 [2,T,T,4] = (albedo rgb, metallic), (roughness, normal xyz), + layout.
+    has_normal: the atlas came with 'normal'; without it the three normal lanes are zero."""
 
-    def __init__(self, tex, layout):
-        self.tex, self.layout = tex, layout
+    def __init__(self, tex, layout, has_normal=False):
+        self.tex, self.layout, self.has_normal = tex, layout, bool(has_normal)
         self.size, self.n_faces, self.pad = layout['size'], layout['n_faces'], layout['pad']
         self.device = tex.device
 
 
 def pack_atlas(atlas, layout=None, device=None):
     """PackedAtlas from what bake_textures returns or load_textures reads (a dict with 'albedo' [T,T,3], 'metallic', 'roughness' [T,T]
-    and 'layout'), or from one [T,T,5] array (albedo, metallic, roughness) with `layout`.  Arrays may be numpy or tensors."""
+    and 'layout'), or from one [T,T,5] array (albedo, metallic, roughness) with `layout`.  Arrays may be numpy or tensors.  A dict's
+    'normal' [T,T,3] (bake_textures(normals='sdf')) goes into lanes y, z, w of plane 1."""
     import torch
     if isinstance(atlas, PackedAtlas):
         return atlas
     dev = torch.device(device) if device is not None else None
     t = lambda a: torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).detach().to(torch.float32)      # noqa: E731
+    normal = None
     if isinstance(atlas, dict):
         layout = atlas['layout'] if layout is None else layout
+        normal = atlas.get('normal')
         al, me, ro = t(atlas['albedo']), t(atlas['metallic']), t(atlas['roughness'])
         if dev is None:
             dev = al.device if al.is_cuda else torch.device('cuda', torch.cuda.current_device())
@@ -186,7 +211,12 @@ def pack_atlas(atlas, layout=None, device=None):
     tex = torch.zeros(2, T, T, 4, dtype=torch.float32, device=five.device)
     tex[0] = five[..., :4]
     tex[1, ..., 0] = five[..., 4]
-    return PackedAtlas(tex, lay)
+    if normal is not None:
+        normal = t(normal).to(five.device)
+        if tuple(normal.shape) != (T, T, 3):
+            raise ValueError(f"pack_atlas: expected [{T},{T},3] normals for this layout, got {tuple(normal.shape)}")
+        tex[1, ..., 1:4] = normal
+    return PackedAtlas(tex, lay, normal is not None)
 
 
 def sample_atlas(atlas, face, uv):
@@ -205,12 +235,33 @@ def sample_atlas(atlas, face, uv):
     return out
 
 
-def texture_gbuffer(scene, face, gbuf, pix, atlas):
+def sample_atlas_normal(atlas, face, uv):
+    """float32 [N,3] on the device: sample_atlas's lookup on the atlas's normal lanes, divided by its length (nu_atlas_sample_normal);
+    zero where the mix has no length in (0, 1e30) -- an atlas without normals, a zero texel -- and for a face id outside the atlas."""
+    import torch
+    from . import _lib as L
+    atlas = pack_atlas(atlas)
+    t = lambda a, dt: torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).detach().to(device=atlas.device, dtype=dt).contiguous()  # noqa: E731
+    face, uv = t(face, torch.int32).reshape(-1), t(uv, torch.float32)
+    if uv.dim() != 2 or uv.shape[1] != 2 or uv.shape[0] != face.shape[0]:
+        raise ValueError(f"sample_atlas_normal: face [N] and uv [N,2] expected, got {tuple(face.shape)} {tuple(uv.shape)}")
+    out = torch.empty(int(face.shape[0]), 3, dtype=torch.float32, device=atlas.device)
+    L.load().nu_atlas_sample_normal(L.ptr(atlas.tex), atlas.size, atlas.n_faces, atlas.pad, L.ptr(face), L.ptr(uv), int(face.shape[0]),
+                                    L.ptr(out), L.stream())
+    return out
+
+
+def texture_gbuffer(scene, face, gbuf, pix, atlas, normals=False):
     """Overwrite the material columns (10..14: albedo, metallic, roughness) of the listed hit rows of a G-buffer of relight.gbuffer(scene,
-    ...) with the atlas's values at the stored hit points, in place; every other column and every unlisted row stays.  -> gbuf."""
+    ...) with the atlas's values at the stored hit points, in place; every other column and every unlisted row stays.  -> gbuf.
+    normals=True: the shading normal (columns 7..9) of those rows is also replaced by the atlas's normal at the hit point,
+    put on the side of the geometric normal (nu_atlas_gbuffer_normal); a row whose lookup has no length keeps its own.  ValueError for
+    an atlas without normals."""
     from . import _lib as L
     if not isinstance(atlas, PackedAtlas):
         raise TypeError("texture_gbuffer takes a PackedAtlas (pack_atlas)")
+    if normals and not atlas.has_normal:
+        raise ValueError("texture_gbuffer: normals=True needs an atlas with 'normal' (bake_textures(normals='sdf'))")
     if atlas.n_faces != int(scene.F.shape[0]):
         raise ValueError(f"the atlas is laid out for {atlas.n_faces} faces, the scene's mesh has {int(scene.F.shape[0])}")
     import torch
@@ -219,19 +270,23 @@ def texture_gbuffer(scene, face, gbuf, pix, atlas):
         raise ValueError("texture_gbuffer: gbuf [*,20] float32, face [*] and pix int32 must be contiguous tensors on the atlas's device")
     L.load().nu_atlas_gbuffer(L.ptr(gbuf), L.ptr(face), L.ptr(pix), int(pix.shape[0]), L.ptr(scene.V), int(scene.V.shape[0]), L.ptr(scene.F),
                               atlas.n_faces, L.ptr(atlas.tex), atlas.size, atlas.pad, L.stream())
+    if normals:
+        L.load().nu_atlas_gbuffer_normal(L.ptr(gbuf), L.ptr(face), L.ptr(pix), int(pix.shape[0]), L.ptr(scene.V), int(scene.V.shape[0]),
+                                         L.ptr(scene.F), atlas.n_faces, L.ptr(atlas.tex), atlas.size, atlas.pad, L.stream())
     return gbuf
 
 
-def predict_textures(renderer, mesh=None, size=2048, which=None, pad=0):
+def predict_textures(renderer, mesh=None, size=2048, which=None, pad=0, normals=None):
     """bake_textures for the mesh predict_materials reads (None: data/meshes/{name}-300000.ply; a PLY path or a (V, F) pair), as float32 /
-    int32 numpy arrays: {'albedo' [T,T,3], 'metallic' [T,T], 'roughness' [T,T], 'face' [T,T], 'uv' [Nf,3,2], 'layout'}."""
+    int32 numpy arrays: {'albedo' [T,T,3], 'metallic' [T,T], 'roughness' [T,T], 'face' [T,T], 'uv' [Nf,3,2], 'layout'}, with
+    normals='sdf' also 'normal' [T,T,3]."""
     import torch
     if mesh is None:
         mesh = os.path.join('data', 'meshes', f"{renderer.cfg['name']}-300000.ply")
     if isinstance(mesh, (str, os.PathLike)):
         from .mesh import read_ply
         mesh = read_ply(mesh)
-    atlas = bake_textures(renderer, mesh[0], mesh[1], size=size, pad=pad, which=which)
+    atlas = bake_textures(renderer, mesh[0], mesh[1], size=size, pad=pad, which=which, normals=normals)
     return {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in atlas.items()}
 
 
@@ -269,9 +324,10 @@ def write_textures(directory, atlas):
     os.makedirs(directory, exist_ok=True)
     lay = _check_layout(atlas['layout'])
     paths = {k: os.path.join(directory, k) for k in ('atlas.npz', 'albedo.png', 'orm.png')}
+    extra = {'normal': _np(atlas['normal']).astype(np.float32)} if atlas.get('normal') is not None else {}
     np.savez(paths['atlas.npz'], albedo=_np(atlas['albedo']).astype(np.float32), metallic=_np(atlas['metallic']).astype(np.float32),
              roughness=_np(atlas['roughness']).astype(np.float32), face=_np(atlas['face']).astype(np.int32),
-             uv=np.asarray(atlas['uv'], np.float32), size=lay['size'], n_faces=lay['n_faces'], pad=lay['pad'])
+             uv=np.asarray(atlas['uv'], np.float32), size=lay['size'], n_faces=lay['n_faces'], pad=lay['pad'], **extra)
     albedo, orm = texture_images(atlas)
     _pillow().fromarray(albedo, 'RGB').save(paths['albedo.png'])
     _pillow().fromarray(orm, 'RGB').save(paths['orm.png'])
@@ -284,13 +340,53 @@ def load_textures(directory, n_faces=None):
     with np.load(path) as z:
         lay = atlas_layout(int(z['n_faces']), int(z['size']), int(z['pad']))
         atlas = {k: np.ascontiguousarray(z[k]) for k in ('albedo', 'metallic', 'roughness', 'face', 'uv')}
+        if 'normal' in z.files:
+            atlas['normal'] = np.ascontiguousarray(z['normal'])
     T = lay['size']
-    if atlas['albedo'].shape != (T, T, 3) or atlas['metallic'].shape != (T, T) or atlas['roughness'].shape != (T, T):
+    if atlas['albedo'].shape != (T, T, 3) or atlas['metallic'].shape != (T, T) or atlas['roughness'].shape != (T, T) \
+            or atlas.get('normal', atlas['albedo']).shape != (T, T, 3):
         raise ValueError(f"{path}: arrays do not have the atlas's size {T}")
     if n_faces is not None and lay['n_faces'] != n_faces:
         raise ValueError(f"{path}: atlas of {lay['n_faces']} faces for a mesh of {n_faces}")
     atlas['layout'] = lay
     return atlas
+
+
+def tangent_frames(V, F):
+    """The flat tangent frame of every face, float64 (Tn, B, N) [Nf,3] each, and `flat` bool [Nf] (faces of zero area).  With
+    e1 = v1 - v0, e2 = v2 - v0: N = unit(e1 x e2); Tn = unit(e1) for an even face (the lower one of its atlas cell, where +u runs
+    v0 -> v1) and -unit(e1) for an odd one (the point-mirrored frame); B = N x Tn.  The handedness is +1 for both -- the mirror is a
+    rotation by 180 degrees, not a reflection.  A face of zero area gets N = (0,0,1), Tn = (1,0,0)."""
+    V, F = np.asarray(_np(V), np.float64).reshape(-1, 3), np.asarray(_np(F), np.int64).reshape(-1, 3)
+    e1, e2 = V[F[:, 1]] - V[F[:, 0]], V[F[:, 2]] - V[F[:, 0]]
+    n = np.cross(e1, e2)
+    ln, l1 = np.linalg.norm(n, axis=1), np.linalg.norm(e1, axis=1)
+    flat = ~((ln > 0.0) & (l1 > 0.0))
+    safe = lambda a, l: a / np.where(flat, 1.0, l)[:, None]      # noqa: E731
+    sign = np.where(np.arange(len(F)) & 1, -1.0, 1.0)[:, None]
+    N = np.where(flat[:, None], np.asarray([0.0, 0.0, 1.0]), safe(n, ln))
+    Tn = np.where(flat[:, None], np.asarray([1.0, 0.0, 0.0]), sign * safe(e1, l1))
+    return Tn, np.cross(N, Tn), N, flat
+
+
+def tangent_normal_image(atlas, V, F, count=False):
+    """uint8 [T,T,3]: the tangent-space normal map of an atlas with 'normal' (object space) for the mesh (V, F), in the flat frames of
+    tangent_frames (host, float64).  Pixel = floor(255 clip(0.5 (n.Tn, n.B, n.N) + 0.5, 0, 1) + 0.5) with the frame of the texel's face
+    (atlas['face']); unowned texels and the texels of zero-area faces are (128, 128, 255), the unperturbed normal.  count=True: ->
+    (image, normal_backfacing), the number of owned texels with n.N <= 0 -- normals that face away from their own face (a mesh far from the zero set, or wound the
+    other way round than f grows): they are encoded as they are, and a viewer lights them from behind."""
+    if atlas.get('normal') is None:
+        raise ValueError("tangent_normal_image: the atlas has no 'normal' (bake_textures(normals='sdf'))")
+    face, n = np.asarray(_np(atlas['face']), np.int64), np.asarray(_np(atlas['normal']), np.float64)
+    Tn, B, N, flat = tangent_frames(V, F)
+    if n.shape != face.shape + (3,) or (face.size and face.max() >= len(Tn)):
+        raise ValueError(f"tangent_normal_image: normal {n.shape}, face {face.shape} for a mesh of {len(Tn)} faces")
+    f = np.maximum(face, 0)
+    own = (face >= 0) & ~flat[f]
+    c = np.stack([(n * Tn[f]).sum(-1), (n * B[f]).sum(-1), (n * N[f]).sum(-1)], -1)
+    img = np.floor(255.0 * np.clip(0.5 * c + 0.5, 0.0, 1.0) + 0.5).astype(np.uint8)
+    img[~own] = (128, 128, 255)
+    return (img, int(np.count_nonzero(own & (c[..., 2] <= 0.0)))) if count else img
 
 
 def _unwelded(V, F, uv, normals):
@@ -330,18 +426,34 @@ def write_obj(path, V, F, uv, normals, directory=None):
     return path, mtl
 
 
-def write_gltf(path, V, F, uv, normals, directory=None):
+def write_gltf(path, V, F, uv, normals, directory=None, normal_map=None):
     """glTF 2.0: PATH (.gltf, JSON) + PATH's .bin.  Vertices are unwelded (3 Nf of them, no index buffer): POSITION, NORMAL and
     TEXCOORD_0 accessors with min / max; one material with baseColorTexture = albedo.png and metallicRoughnessTexture = orm.png of
     `directory` (default: the file's own), referenced by relative URI, both factors 1; the sampler is LINEAR / LINEAR without mip
-    filter (the atlas's gutter is sized for bilinear taps) and CLAMP_TO_EDGE."""
+    filter (the atlas's gutter is sized for bilinear taps) and CLAMP_TO_EDGE.
+    normal_map: an atlas dict with 'normal' (None: the file above, byte for byte).  Its tangent-space image
+    (tangent_normal_image) is written as normal.png beside the other textures and named as the material's normalTexture (scale 1); every
+    face corner then carries NORMAL = the face's flat normal instead of the vertex normal, and a TANGENT accessor (VEC4) holds (Tn, 1) of
+    tangent_frames.  The frame is constant per face and in the file, so bitangent = cross(NORMAL, TANGENT.xyz) TANGENT.w gives back the
+    baked object-space normal whatever the viewer's tangent generator or interpolation."""
     path = str(path)
     P, N, T2 = _unwelded(V, F, uv, normals)
     base = os.path.dirname(os.path.abspath(path))
     rel = os.path.relpath(os.path.abspath(directory), base) if directory is not None else '.'
     tex = lambda name: name if rel == '.' else (rel + '/' + name).replace(os.sep, '/')      # noqa: E731
     bin_path = os.path.splitext(path)[0] + '.bin'
+    tangent = None
+    if normal_map is not None:
+        from .mask_render import _pillow
+        image = tangent_normal_image(normal_map, V, F)
+        Tn, _, Nf, _ = tangent_frames(V, F)
+        N = np.ascontiguousarray(np.repeat(Nf, 3, axis=0), np.float32)
+        tangent = np.ascontiguousarray(np.repeat(np.concatenate([Tn, np.ones((len(Tn), 1))], 1), 3, axis=0), np.float32)
+        os.makedirs(base if directory is None else directory, exist_ok=True)
+        _pillow().fromarray(image, 'RGB').save(os.path.join(base if directory is None else directory, 'normal.png'))
     blobs = [P.astype('<f4').tobytes(), N.astype('<f4').tobytes(), T2.astype('<f4').tobytes()]
+    if tangent is not None:
+        blobs.append(tangent.astype('<f4').tobytes())
     offsets = np.concatenate([[0], np.cumsum([len(b) for b in blobs])]).tolist()
     with open(bin_path, 'wb') as fh:
         for b in blobs:
@@ -361,11 +473,17 @@ def write_gltf(path, V, F, uv, normals, directory=None):
         'samplers': [{'magFilter': 9729, 'minFilter': 9729, 'wrapS': 33071, 'wrapT': 33071}],
         'images': [{'uri': tex('albedo.png')}, {'uri': tex('orm.png')}],
         'buffers': [{'uri': os.path.basename(bin_path), 'byteLength': offsets[-1]}],
-        'bufferViews': [{'buffer': 0, 'byteOffset': offsets[i], 'byteLength': len(blobs[i]), 'target': 34962} for i in range(3)],
+        'bufferViews': [{'buffer': 0, 'byteOffset': offsets[i], 'byteLength': len(blobs[i]), 'target': 34962} for i in range(len(blobs))],
         'accessors': [dict({'bufferView': 0, 'componentType': 5126, 'count': n, 'type': 'VEC3'}, **bounds(P)),
                       dict({'bufferView': 1, 'componentType': 5126, 'count': n, 'type': 'VEC3'}, **bounds(N)),
                       dict({'bufferView': 2, 'componentType': 5126, 'count': n, 'type': 'VEC2'}, **bounds(T2))],
     }
+    if tangent is not None:
+        doc['meshes'][0]['primitives'][0]['attributes']['TANGENT'] = 3
+        doc['accessors'].append({'bufferView': 3, 'componentType': 5126, 'count': n, 'type': 'VEC4'})
+        doc['materials'][0]['normalTexture'] = {'index': 2, 'scale': 1.0}
+        doc['textures'].append({'sampler': 0, 'source': 2})
+        doc['images'].append({'uri': tex('normal.png')})
     with open(path, 'w') as fh:
         json.dump(doc, fh, indent=1)
     return path, bin_path
