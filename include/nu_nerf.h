@@ -127,6 +127,11 @@ int nu_gemm_nt_ex(const NuGemmNT* g, hipStream_t stream);
  * the IoR / thickness pair of stage 2 (field.py:1046-1087).  Results are bit-identical to n calls of nu_gemm_nt_ex. */
 #define NU_NT_BATCH_MAX 8
 int nu_gemm_nt_batch(const NuGemmNT* problems_host, int n, hipStream_t stream);
+/* Which row-tile height a launch of these problems takes (host only: launches nothing, reads no device memory).  64 or 128: the tiles of
+ * the exact-fp32 kernel that nu_gemm_nt_ex (n == 1) or nu_gemm_nt_batch (the first run of the list that shares a launch) picks, by the
+ * very code the dispatch decides with.  0: the launch does not reach that kernel (another arithmetic mode, M <= 0, n == 0).
+ * Negative NU_ERR_*: arguments the launch itself rejects. */
+int nu_gemm_nt_tile_rows(const NuGemmNT* problems_host, int n);
 long long nu_wgrad_workspace_bytes(int N1, int N2, int S, int groups);
 /* the split (number of deterministic partial slabs) the library's own sequencing uses for a weight gradient of this shape */
 int nu_wgrad_pick_split(int P, int N1, int N2, int groups, int prec);

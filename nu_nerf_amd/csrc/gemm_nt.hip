@@ -458,6 +458,36 @@ static bool nt_small_tiles(long long t128, long long t64) {
     auto round_eff = [&](long long tiles) { return (double)tiles / (double)(nu_cdivl(tiles, 512) * 512); };
     return t128 < 512 || 0.95 * round_eff(t64) > round_eff(t128);
 }
+// The tile counts of the exact-fp32 problems that share one launch, groups included, and the tile height they take.  The single
+// launch, the batch launch and nu_gemm_nt_tile_rows all decide here.
+struct NtTiles {
+    long long t128 = 0, t64 = 0;
+    void add(const NuGemmNT& g) {
+        const long long cols = (long long)nu_cdiv(g.N, TBN) * (g.groups > 0 ? g.groups : 1);
+        t128 += nu_cdiv(g.M, TBM) * cols;
+        t64 += nu_cdiv(g.M, 64) * cols;
+    }
+    bool small() const { return nt_small_tiles(t128, t64); }
+};
+static bool nt_epi_known(int epi) { return epi >= 0 && epi < NU_EPI_COUNT; }
+
+// The tiles write the zeros of columns [N, zero_to) only as far as the grid reaches, ceil128(N).  A zero_to beyond that (N a multiple
+// of 128 with pad columns behind it: no launch of the engine) is filled here, on the same stream, for every kernel of the dispatch.
+static int nt_zero_tail(const NuGemmNT& g, hipStream_t stream) {
+    const int np = nu_rup(g.N, TBN);
+    if (g.zero_to <= np || g.M <= 0) return NU_OK;
+    const size_t eb = ((g.bf16 & 3) == 1 && (g.bf16 & NU_GEMM_C16)) ? 2 : 4;        // element bytes of C / C2
+    const int groups = g.groups > 0 ? g.groups : 1;
+    for (int z = 0; z < groups; ++z) {
+        char* c = reinterpret_cast<char*>(g.C) + ((long long)z * g.sC + np) * eb;
+        if (hipMemset2DAsync(c, g.ldc * eb, 0, (g.zero_to - np) * eb, g.M, stream) != hipSuccess) return NU_ERR_LAUNCH;
+        if (g.epi == NU_EPI_Q_SP && g.C2) {
+            c = reinterpret_cast<char*>(g.C2) + ((long long)z * g.sC2 + np) * eb;
+            if (hipMemset2DAsync(c, g.ldc2 * eb, 0, (g.zero_to - np) * eb, g.M, stream) != hipSuccess) return NU_ERR_LAUNCH;
+        }
+    }
+    return NU_OK;
+}
 
 // Dispatch, by arithmetic mode (g.bf16 & 3):
 //   bf16 with bf16 storage (NU_GEMM_B16)      -> gemm_nt16b_kernel (gemm_nt16.hip)
@@ -469,6 +499,9 @@ int nu_gemm_nt_launch(const NuGemmNT& g, hipStream_t stream) {
     if (g.M <= 0) return NU_OK;
     const int rc = nt_check(g);
     if (rc != NU_OK) return rc;
+    if (!nt_epi_known(g.epi)) return NU_ERR_ARG;
+    const int zrc = nt_zero_tail(g, stream);
+    if (zrc != NU_OK) return zrc;
     const int ntn = nu_cdiv(g.N, TBN);
     const long long nslots = (long long)nu_rup(nu_cdiv(g.M, TBM), 8) * ntn;      // 128-row tiles
     const int groups = g.groups > 0 ? g.groups : 1;
@@ -484,8 +517,9 @@ int nu_gemm_nt_launch(const NuGemmNT& g, hipStream_t stream) {
         ((g.bf16 & NU_GEMM_PRESPLIT_ALWAYS) || (nt6_epi && (long long)nu_cdiv(g.M, TBM) * nu_cdiv(g.N, 256) * groups >= 320)))
         return nu_gemm_nt6_launch(g, groups, stream);
     if (prec == 0) {
-        const long long t128 = (long long)nu_cdiv(g.M, TBM) * ntn * groups, t64 = (long long)nu_cdiv(g.M, 64) * ntn * groups;
-        const bool small = nt_small_tiles(t128, t64);
+        NtTiles tiles;
+        tiles.add(g);
+        const bool small = tiles.small();
         const long long nslots2 = small ? (long long)nu_rup(nu_cdiv(g.M, 64), 8) * ntn : nslots;
         long long per = nu_rup(nu_cdiv(512, groups), 8);       // two workgroups per CU
         if (per > nslots2) per = nslots2;
@@ -528,6 +562,61 @@ int nu_gemm_nt_launch(const NuGemmNT& g, hipStream_t stream) {
     return nu_launch_status();
 }
 
+// The longest run of problems starting at i that one batch launch can take, expanded into its groups: b.p[0 .. nb), their tile
+// counts, and `last`, the first problem behind the run.  nb < 2: nothing to share a launch with.
+static int nt_batch_run(const NuGemmNT* probs, int i, int n, NuGemmNTBatch& b, int& nb, int& last, NtTiles& tiles) {
+    nb = 0;
+    last = i;
+    tiles = NtTiles();
+    const int epi = probs[i].epi;
+    const bool epi_ok = epi == NU_EPI_BIAS_NONE || epi == NU_EPI_BIAS_RELU || epi == NU_EPI_MUL_DRELU || epi == NU_EPI_PLAIN;
+    for (int k = i; k < n && epi_ok; ++k) {
+        const NuGemmNT& g = probs[k];
+        if (g.M <= 0) { last = k + 1; continue; }
+        const int groups = g.groups > 0 ? g.groups : 1;
+        if (g.epi != epi || (g.bf16 & 3) != 0 || (g.bf16 & ~3) != 0 || nb + groups > NU_NT_BATCH_MAX) break;
+        const int rc = nt_check(g);
+        if (rc != NU_OK) return rc;
+        const int ntn = nu_cdiv(g.N, TBN);
+        for (int z = 0; z < groups; ++z) {
+            NuGemmNT& q = b.p[nb++];
+            q = g;
+            q.groups = 1;
+            q.A = g.A + z * g.sA; q.B = g.B + z * g.sB; q.C = g.C + z * g.sC;
+            q.C2 = g.C2 ? g.C2 + z * g.sC2 : nullptr; q.bias = g.bias ? g.bias + z * g.sBias : nullptr;
+            q.H = g.H ? g.H + z * g.sH : nullptr; q.D = g.D ? g.D + z * g.sD : nullptr; q.Cadd = g.Cadd ? g.Cadd + z * g.sCadd : nullptr;
+            q.mask_ct0 = g.mask_ct0 + z * ntn;
+        }
+        tiles.add(g);
+        last = k + 1;
+    }
+    return NU_OK;
+}
+
+// The row-tile height of a single exact-fp32 launch (0: another arithmetic mode, or nothing to launch), after its argument checks
+static int nt_single_tile_rows(const NuGemmNT& g) {
+    if (g.M <= 0) return 0;
+    const int rc = nt_check(g);
+    if (rc != NU_OK) return rc;
+    if (!nt_epi_known(g.epi)) return NU_ERR_ARG;
+    if ((g.bf16 & 3) != 0) return 0;
+    NtTiles tiles;
+    tiles.add(g);
+    return tiles.small() ? 64 : 128;
+}
+
+extern "C" int nu_gemm_nt_tile_rows(const NuGemmNT* problems_host, int n) {
+    if (n < 0 || (n > 0 && problems_host == nullptr)) return NU_ERR_ARG;
+    if (n == 0) return 0;
+    NuGemmNTBatch b;
+    NtTiles tiles;
+    int nb = 0, last = 0;
+    const int rc = nt_batch_run(problems_host, 0, n, b, nb, last, tiles);
+    if (rc != NU_OK) return rc;
+    if (nb < 2) return nt_single_tile_rows(problems_host[0]);
+    return tiles.small() ? 64 : 128;
+}
+
 // Several independent problems in ONE persistent launch (exact fp32, one epilogue kind).  A problem with `groups` > 1 is expanded
 // into its groups (operand pointers advanced by the strides, sign-bit column tiles by mask_ct0).  Whatever the batch kernel does
 // not cover -- other arithmetic modes, epilogue kinds without a batch build -- runs as one launch per problem: same
@@ -535,40 +624,19 @@ int nu_gemm_nt_launch(const NuGemmNT& g, hipStream_t stream) {
 int nu_gemm_nt_batch_launch(const NuGemmNT* probs, int n, hipStream_t stream) {
     int i = 0;
     while (i < n) {
-        // the longest run of problems starting at i that one launch can take
         NuGemmNTBatch b;
+        NtTiles tiles;
         int nb = 0, last = i;
-        long long t128 = 0, t64 = 0;
+        const int run_rc = nt_batch_run(probs, i, n, b, nb, last, tiles);
+        if (run_rc != NU_OK) return run_rc;
         const int epi = probs[i].epi;
-        const bool epi_ok = epi == NU_EPI_BIAS_NONE || epi == NU_EPI_BIAS_RELU || epi == NU_EPI_MUL_DRELU || epi == NU_EPI_PLAIN;
-        for (int k = i; k < n && epi_ok; ++k) {
-            const NuGemmNT& g = probs[k];
-            if (g.M <= 0) { last = k + 1; continue; }
-            const int groups = g.groups > 0 ? g.groups : 1;
-            if (g.epi != epi || (g.bf16 & 3) != 0 || (g.bf16 & ~3) != 0 || nb + groups > NU_NT_BATCH_MAX) break;
-            const int rc = nt_check(g);
-            if (rc != NU_OK) return rc;
-            const int ntn = nu_cdiv(g.N, TBN);
-            for (int z = 0; z < groups; ++z) {
-                NuGemmNT& q = b.p[nb++];
-                q = g;
-                q.groups = 1;
-                q.A = g.A + z * g.sA; q.B = g.B + z * g.sB; q.C = g.C + z * g.sC;
-                q.C2 = g.C2 ? g.C2 + z * g.sC2 : nullptr; q.bias = g.bias ? g.bias + z * g.sBias : nullptr;
-                q.H = g.H ? g.H + z * g.sH : nullptr; q.D = g.D ? g.D + z * g.sD : nullptr; q.Cadd = g.Cadd ? g.Cadd + z * g.sCadd : nullptr;
-                q.mask_ct0 = g.mask_ct0 + z * ntn;
-                t128 += (long long)nu_cdiv(g.M, TBM) * ntn;
-                t64 += (long long)nu_cdiv(g.M, 64) * ntn;
-            }
-            last = k + 1;
-        }
         if (nb < 2) {                  // nothing to share a launch with: the single-problem path (all modes)
             const int rc = nu_gemm_nt_launch(probs[i], stream);
             if (rc != NU_OK) return rc;
             ++i;
             continue;
         }
-        const bool small = nt_small_tiles(t128, t64);
+        const bool small = tiles.small();
         long long slots = 0;
         for (int k = 0; k < nb; ++k) {
             b.slot0[k] = (int)slots;
@@ -592,6 +660,10 @@ int nu_gemm_nt_batch_launch(const NuGemmNT* probs, int n, hipStream_t stream) {
         }
         const int rc = nu_launch_status();
         if (rc != NU_OK) return rc;
+        for (int k = i; k < last; ++k) {
+            const int zrc = nt_zero_tail(probs[k], stream);
+            if (zrc != NU_OK) return zrc;
+        }
         i = last;
     }
     return NU_OK;

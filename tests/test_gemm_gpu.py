@@ -194,7 +194,7 @@ def test_relu_sign_bits_replace_the_activation_in_the_backward_epilogues(gpu):
     torch.testing.assert_close(out3.double(), want, rtol=2e-5, atol=2e-5)
 
 
-@pytest.mark.parametrize("M", [66048, 65990])
+@pytest.mark.parametrize("M", [64000, 63990])
 def test_epilogue_fast_path_copies_on_128_row_tiles(gpu, M):
     """The interior slabs of a launch run one of up to three copies of the epilogue's fast path (gemm_epi.h): sign-bit words
     (writer and reader), plain columns past act_cols, auxiliary rows -- here all three in launches big enough for the 128-row tiles
@@ -212,6 +212,7 @@ def test_epilogue_fast_path_copies_on_128_row_tiles(gpu, M):
     mask = torch.zeros(((M + 127) // 128) * 2 * 256, dtype=torch.int64, device=gpu)
     g = GemmNT(addr(A), K, addr(_packB(W, K)), K, M, 256, K, addr(Hout), 256, 0, 0, addr(bias), 0, 0, 0, 0, 0, 0, 0, 0, 1.0, 1,
                0, 0, 0, 0, 0, 0, 0, 0, 1, 0, mask.data_ptr(), 2, 0)
+    assert lib.nu_gemm_nt_tile_rows(ctypes.byref(g), 1) == 128
     L.check(lib.nu_gemm_nt_ex(ctypes.byref(g), L.stream()), "writer")
     ref_h = torch.relu(A.double() @ W.double().t() + bias.double())
     torch.testing.assert_close(Hout.double(), ref_h, rtol=2e-5, atol=2e-5)
@@ -223,6 +224,7 @@ def test_epilogue_fast_path_copies_on_128_row_tiles(gpu, M):
     out = torch.full((M, 384), float("nan"), device=gpu)
     g = GemmNT(addr(dA), 256, addr(W3), 256, M, 384, 256, addr(out), 384, 0, 0, 0, addr(poison), 256, 0, 0, 0, 0, 384, 256, 1.0, 1,
                0, 0, 0, 0, 0, 0, 0, 0, 3, 0, mask.data_ptr(), 2, 0)
+    assert lib.nu_gemm_nt_tile_rows(ctypes.byref(g), 1) == 128
     L.check(lib.nu_gemm_nt_ex(ctypes.byref(g), L.stream()), "reader + plain")
     v = dA.double() @ W3.double().t()
     torch.testing.assert_close(out.double(), torch.cat([v[:, :256] * pos, v[:, 256:]], 1), rtol=2e-5, atol=2e-5)
@@ -230,6 +232,7 @@ def test_epilogue_fast_path_copies_on_128_row_tiles(gpu, M):
     out_h = torch.full((M, 384), float("nan"), device=gpu)
     g = GemmNT(addr(dA), 256, addr(W3), 256, M, 384, 256, addr(out_h), 384, 0, 0, 0, addr(Hout), 256, 0, 0, 0, 0, 384, 256, 1.0, 1,
                0, 0, 0, 0, 0, 0, 0, 0, 3, 0, 0, 0, 0)
+    assert lib.nu_gemm_nt_tile_rows(ctypes.byref(g), 1) == 128
     L.check(lib.nu_gemm_nt_ex(ctypes.byref(g), L.stream()), "reader from H")
     assert torch.equal(out_h, out)
     # B_RELU on the sign bits with Cadd
@@ -237,6 +240,7 @@ def test_epilogue_fast_path_copies_on_128_row_tiles(gpu, M):
     out2 = torch.full((M, 256), float("nan"), device=gpu)
     g = GemmNT(addr(dA), 256, addr(W3), 256, M, 256, 256, addr(out2), 256, 0, 0, 0, addr(poison), 256, 0, 0, addr(Cadd), 256, 0, 0, 1.0, 1,
                0, 0, 0, 0, 0, 0, 0, 0, 8, 0, mask.data_ptr(), 2, 0)
+    assert lib.nu_gemm_nt_tile_rows(ctypes.byref(g), 1) == 128
     L.check(lib.nu_gemm_nt_ex(ctypes.byref(g), L.stream()), "b_relu")
     torch.testing.assert_close(out2.double(), v[:, :256] * pos + Cadd.double(), rtol=2e-5, atol=2e-5)
 
@@ -258,6 +262,7 @@ def test_nt_batch_is_bit_identical_to_one_launch_per_problem(gpu, rows):
     lib = L.load()
     torch.manual_seed(sum(rows))
     Ks = (96, 128, 256, 160)
+    tile_rows = {40000: 128, 3000: 64, 128: 64}[rows[0]]      # of both levels' lists (nt_small_tiles over the summed tiles)
 
     def run(batched):
         torch.manual_seed(11)
@@ -305,6 +310,7 @@ def test_nt_batch_is_bit_identical_to_one_launch_per_problem(gpu, rows):
         for level in (probs, back):
             if batched:
                 arr = (GemmNT * len(level))(*level)
+                assert lib.nu_gemm_nt_tile_rows(arr, len(level)) == tile_rows
                 L.check(lib.nu_gemm_nt_batch(arr, len(level), L.stream()), "nu_gemm_nt_batch")
             else:
                 for g in level:
