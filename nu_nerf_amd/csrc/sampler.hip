@@ -168,6 +168,8 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__
             const int mid = (lo + hi) >> 1;
             if (s_c[w][mid] > u) hi = mid; else lo = mid + 1;
         }
+        // the last knot is 1 by definition but its fp32 running sum can end an ulp above: u = 1 is the last depth either way
+        if (u >= 1.0f) lo = sn;
         const int below = lo - 1 > 0 ? lo - 1 : 0;
         const int above = lo < sn - 1 ? lo : sn - 1;
         const float c0 = s_c[w][below], c1 = s_c[w][above];
