@@ -889,6 +889,37 @@ int nu_light_bake_fwd(const NuShadeNet* net, const float* dirs, const float* kin
                       int probe, float* light, float* direct, float* indirect, float* occ, float* enc_dbg, float* raw_dbg,
                       hipStream_t stream);
 
+/* The appearance the shading network learned, at a caller's surface points, as ONE fully-fused no-gradient kernel
+ * (csrc/surface_shade.hip): AppShadingNetwork.forward in its stage-1 form (network/field.py:684-777; AppShadingNetwork_SpecInner is the
+ * same form) on explicit rows -- n^, v^, NoV, r = 2 NoV n^ - v^, rho = sigmoid(Mraw[:, 1]); the seven predictor rows outer_light x 3
+ * (IDE(n^, 1) | IDE(r, rho) | IDE(r, 0), + the sphere points with net->sphere), inner_light x 2, inner_weight, refrac_light;
+ * exp(min(., exp_max)); occlusion mix; split-sum FG table (bilinear, clamp); Schlick; transmission mix; sRGB.  One launch for any P, no
+ * workspace, no host read; it reads the fp32 packed tables only.
+ *   X [P, x_ld] the point, V [P, v_ld] the view direction TOWARDS the camera, Nrm [P, n_ld] the normal (neither is normalised by the
+ *   caller; the first three floats of a row, every leading dimension >= 3); Mraw [P, ldm >= 6] the raw material heads in the layered
+ *   layout (metallic, roughness, albedo x 3, transmission).  pos_freq: the network's light_pos_freq (<= 8).  refrac_exp_max: the cap
+ *   shade() applies to the raw refrac_light head of AppShadingNetwork_SpecInner (-0.2); pass net->exp_max for no extra cap.
+ *   flags & NU_SHADE_LINEAR: `color` skips linear_to_srgb.
+ *   Outputs, every pointer may be NULL: color [P,3]; the validation images of field.py:751-770 BEFORE their display clamps, sRGB
+ *   applied where the reference applies it: diffuse_color = srgb(diffuse), specular_color = srgb(specular) (1 - T) + F light0 T,
+ *   indirect_light = indirect occ (linear), refraction_light = srgb((1 - F) refraction T) [P,3], occ_prob = 0.5 raw + 0.5,
+ *   reflection_weight = F [P]; and the two light images LINEAR: diffuse_light = exp(min(outer_light(IDE(n^, 1)), exp_max)),
+ *   specular_light = light0, the blended roughness-0 specular light (the reference's pictures are clamp(srgb(.)) of them).
+ *   The human-light stack is NEVER evaluated: for a model trained with shader_config.human_light the photographer's term is left
+ *   out (human_weight = 0), as nu_light_bake_fwd leaves it out.
+ *   Exact fp32 in the k order of the layered path: the encoded rows are the bits of nu_s2_shade_encode_fwd, the raw heads those of
+ *   nu_gemm_nt + nu_skinny_fwd, the colour those of nu_shade_combine_fwd on them.
+ *   Test outputs: enc_dbg [P, 3 ld_ol + 2 * 128 + 96 + ld_rl]: per point its OLin rows (diffuse | specular | mirror), ILin rows
+ *   (specular | mirror), IWin row and RLin row; raw_dbg [P,20]: the heads before activation in the same order (3 3 3 3 3 1 3, then 0).
+ *   NU_ERR_ARG: net / X / V / Nrm / Mraw NULL, P < 0, a leading dimension < 3, ldm < 6, unknown flags, pos_freq that is not the
+ *   network's (or > 8), tables that are not the four 3 x 256 predictors with the rows above, no FG table.  P == 0 launches nothing. */
+#define NU_SHADE_LINEAR 1
+int nu_surface_shade_fwd(const NuShadeNet* net, const float* X, int x_ld, const float* V, int v_ld, const float* Nrm, int n_ld,
+                         const float* Mraw, int ldm, int P, int pos_freq, float refrac_exp_max, int flags, float* color,
+                         float* diffuse_color, float* specular_color, float* diffuse_light, float* specular_light, float* indirect_light,
+                         float* refraction_light, float* occ_prob, float* reflection_weight, float* enc_dbg, float* raw_dbg,
+                         hipStream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * Fused loss assembly: from the renderer's per-ray outputs to the scalar the trainer back-propagates, for
  * the loss set of the shipped stage-1 configs -- white background + clamp (renderer_zerothick.py:783-787), charbonier RGB

@@ -780,6 +780,26 @@ class Stage1Engine:
                                    1 if probe else 0, addr(light), addr(direct), addr(indirect), addr(occ), addr(enc), addr(raw),
                                    self.stream())
 
+    # ------------------------------------------------------------------ surface shade
+    def surface_shade(self, X, x_ld, V, v_ld, Nrm, n_ld, Mraw, ldm, P, *, linear=False, out=None, enc=None, raw=None):
+        """Stage-1-form shading of P explicit surface points in ONE kernel (csrc/surface_shade.hip).  X, V, Nrm, Mraw: device addresses
+        of [P, x_ld] points, [P, v_ld] view directions towards the camera, [P, n_ld] normals (neither normalised) and [P, ldm >= 6] raw
+        material heads.  out: {name: fp32 tensor} of the kernel's outputs to write ('color' and the terms of nu_surface_shade_fwd in
+        include/nu_nerf.h; a name left out is not written).  The refraction light is capped at this engine's `refrac_exp_max` (the
+        SpecInner network's -0.2; otherwise light_exp_max).  Reads the fp32 packed tables, which pack() writes in every mlp_dtype.
+        enc [P, 3 ld_ol + 352 + ld_rl] / raw [P,20]: the kernel's test outputs (encoded rows; heads before activation)."""
+        if self._desc_dev is None or self._ptr_sig != self._signature():
+            self._upload_descs()
+        out = out or {}
+        names = ('color', 'diffuse_color', 'specular_color', 'diffuse_light', 'specular_light', 'indirect_light', 'refraction_light',
+                 'occ_prob', 'reflection_weight')
+        unknown = set(out) - set(names)
+        if unknown:
+            raise ValueError(f"surface_shade: unknown outputs {sorted(unknown)}")
+        self.lib.nu_surface_shade_fwd(ctypes.byref(self._shade_net), X, x_ld, V, v_ld, Nrm, n_ld, Mraw, ldm, P, self.light_pos_freq,
+                                      float(self.cfg.get('refrac_exp_max', self.exp_max)), L.NU_SHADE_LINEAR if linear else 0,
+                                      *[addr(out.get(k)) for k in names], addr(enc), addr(raw), self.stream())
+
     # ------------------------------------------------------------------ SDF network
     def sdf_forward(self, X, x_ld, P, *, keep=True, want_feat=True):
         """SDF MLP forward on P points (X: device address of [P, x_ld] rows whose first 3 floats are x).

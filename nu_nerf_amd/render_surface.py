@@ -9,7 +9,10 @@ and every requested AOV, DIR/{k}_{aov}.png is written, plus DIR/{k}_depth.npy (f
 --cam_dist; relight.intrinsics at --hw).  --poses FILE.npz: 'poses' [n,3,4] world -> camera and optionally 'K' [3,3].  --out defaults to
 data/surface/{name}-{step}.  --stage2: a stage-2 config; --which inner (default) traces the inner SDF, outer the stage-1 SDF it
 carries.  PNG encoding (RGBA, alpha = the mask): depth scaled to the frame's hit range, normal and position as 0.5 + 0.5 v, materials
-as they are, curvatures as 0.5 + k / 20 clipped.  Prints one JSON line: the output directory, the frame count and the rays hit per frame.
+as they are, curvatures as 0.5 + k / 20 clipped.  The learned appearance (sdf_trace.SHADING_AOVS, one fused shading kernel on the hit
+pixels, surface_shade.py): `--aovs rgb` writes DIR/{k}_rgb.png as RGBA with the hit mask as alpha; the other shading images are RGB or grey
+PNGs, 0 where missed.  Only the traced surface is shaded: no background model is evaluated, no human light, and a stage-2 shell is not seen
+through.  Prints one JSON line: the output directory, the frame count and the rays hit per frame.
 """
 import argparse
 import json
@@ -20,7 +23,7 @@ DEFAULT_AOVS = ('depth', 'normal', 'mask')
 
 
 def parse_args(argv=None):
-    from .sdf_trace import AOVS
+    from .sdf_trace import ALL_AOVS as AOVS
     ap = argparse.ArgumentParser(prog="python -m nu_nerf_amd.render_surface", description=__doc__.split("\n\n")[1])
     ap.add_argument('--cfg', type=str, required=True, help="training config (YAML)")
     ap.add_argument('--ckpt', type=str, default=None, help="checkpoint (default data/model/{name}/model.pth; 'none': the initialised model)")
@@ -109,6 +112,12 @@ def to_rgba(aov, img, mask):
     return np.concatenate([np.where(hit[:, :, None] | (aov == 'mask'), rgb, 0).astype(np.uint8), alpha[:, :, None]], 2)
 
 
+def to_plain(img):
+    """uint8 numpy [h,w,3] or [h,w] of a shading AOV already in [0, 1] (0 where missed): what the RGB / grey PNGs hold."""
+    import numpy as np
+    return (np.clip(np.nan_to_num(np.asarray(img, np.float32)), 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+
+
 def main(argv=None):
     flags = parse_args(argv)
     import numpy as np
@@ -116,7 +125,8 @@ def main(argv=None):
     import yaml
     from .extract_mesh import _renderer
     from .relight import write_png
-    from .sdf_trace import render_surface
+    from .mask_render import _pillow
+    from .sdf_trace import SHADING_AOVS, render_surface
     from .train_glue import load_checkpoint
 
     with open(flags.cfg) as fh:
@@ -145,7 +155,10 @@ def main(argv=None):
         imgs = {a: v.cpu().numpy() for a, v in imgs.items()}
         paths = frame_paths(out, k, flags.aovs)
         for a in flags.aovs:
-            write_png(paths[a], to_rgba(a, imgs[a], imgs['mask']))
+            if a in SHADING_AOVS and a != 'rgb':
+                _pillow().fromarray(to_plain(imgs[a])).save(paths[a])
+            else:
+                write_png(paths[a], to_rgba(a, imgs[a], imgs['mask']))
         if 'depth' in flags.aovs:
             np.save(paths['depth.npy'], np.ascontiguousarray(imgs['depth'], np.float32))
         hits.append(int((imgs['mask'] > 0).sum()))

@@ -357,6 +357,12 @@ class NeROShapeRenderer(nn.Module):
         from .sdf_trace import render_surface
         return render_surface(self, K, pose, h, w, **kw)
 
+    def shade_points(self, points, view_dirs, normals=None, **kw):
+        """The learned appearance at surface points (device tensors [P, >= 3]; view_dirs towards the camera): {'rgb' [P,3], ...} by one
+        fused shading kernel after the fused SDF gradient and material bake (surface_shade.py)."""
+        from .surface_shade import shade_points
+        return shade_points(self, points, view_dirs, normals, **kw)
+
     # ---- data ----------------------------------------------------------------------------------
     def _init_dataset(self):
         """Ray-batch store (renderer_zerothick.py:167-190).  `database_name: synthetic/<n_rays>` builds the seeded synthetic

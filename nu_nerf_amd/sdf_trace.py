@@ -11,8 +11,9 @@ include/nu_nerf.h.
 
 trace_rays      rays -> {'pos' [R,3], 't' [R], 'sdf' [R] (the last evaluation), 'iters' [R] int32, 'hit' [R] uint8 (0 / 1)}
 render_surface  a pinhole camera (mask_render.pinhole_rays: K, world -> camera pose) -> images of the traced surface: mask, depth,
-                position, normal, and on request albedo / roughness / metallic (materials.bake_materials) and mean / Gaussian curvature
-                (curvature.bake_curvature), evaluated at the hit points only.
+                position, normal, and on request albedo / roughness / metallic (materials.bake_materials), mean / Gaussian curvature
+                (curvature.bake_curvature) and the learned appearance (SHADING_AOVS: 'rgb' and the shading terms,
+                surface_shade.shade_points), evaluated at the hit points only.
 'outer' is the stage-1 SDF, 'inner' a stage-2 model's inner SDF, as in materials.py.
 """
 import torch
@@ -24,7 +25,13 @@ GEOMETRY_AOVS = ('mask', 'depth', 'position', 'normal')
 MATERIAL_AOVS = ('albedo', 'roughness', 'metallic')
 CURVATURE_AOVS = ('mean_curvature', 'gaussian_curvature')
 AOVS = GEOMETRY_AOVS + MATERIAL_AOVS + CURVATURE_AOVS
-_CHANNELS = {'position': 3, 'normal': 3, 'albedo': 3}
+# the learned appearance at the hit points (surface_shade.py): the colour and the reference's validation images (field.py:751-770)
+SHADING_AOVS = ('rgb', 'diffuse_color', 'specular_color', 'diffuse_light', 'specular_light', 'occ_prob', 'indirect_light',
+                'refraction_light', 'reflection_weight')
+ALL_AOVS = AOVS + SHADING_AOVS
+_CHANNELS = {'position': 3, 'normal': 3, 'albedo': 3, 'rgb': 3, 'diffuse_color': 3, 'specular_color': 3, 'diffuse_light': 3,
+             'specular_light': 3, 'indirect_light': 3, 'refraction_light': 3}
+_SRGB_AOVS = ('diffuse_light', 'specular_light')       # the kernel returns these two linear; their pictures are clamp(linear_to_srgb(.))
 
 
 def _fail(msg):
@@ -87,9 +94,9 @@ def trace_rays(renderer, rays_o, rays_d, *, which=None, mask=None, max_iter=200,
 
 def _check_aovs(aovs):
     aovs = (aovs,) if isinstance(aovs, str) else tuple(aovs)
-    bad = [a for a in aovs if a not in AOVS]
+    bad = [a for a in aovs if a not in ALL_AOVS]
     if bad or not aovs:
-        raise ValueError(f"aovs={aovs!r}: expected one or more of {AOVS}")
+        raise ValueError(f"aovs={aovs!r}: expected one or more of {ALL_AOVS}")
     return aovs
 
 
@@ -100,6 +107,12 @@ def render_surface(renderer, K, pose, h, w, *, which=None, aovs=('depth', 'norma
     material bake at the hit points only.  -> dict of device tensors, one per name in `aovs`:
       'mask' [h,w] uint8 (255 = hit)        'depth' [h,w] (t along the unit ray, 0 where missed)      'position', 'normal' [h,w,3]
       'albedo' [h,w,3], 'roughness', 'metallic' [h,w]      'mean_curvature', 'gaussian_curvature' [h,w]      (all 0 where missed)
+    and the learned appearance at the hit points (SHADING_AOVS; surface_shade.shade_points with view direction = -ray direction, one
+    fused shading kernel per pass), clamped to [0, 1] as the reference's validation pictures are:
+      'rgb' [h,w,3]      'diffuse_color', 'specular_color', 'indirect_light', 'refraction_light' [h,w,3]
+      'diffuse_light', 'specular_light' [h,w,3] (sRGB of the diffuse query's light / of the roughness-0 specular light)
+      'occ_prob', 'reflection_weight' [h,w]
+    Only this one surface is shaded: no human light, no background model, no refraction through a stage-2 shell.
     chunk: rays per pass (None: the whole image at once); the result does not depend on it.  trace_kw: max_iter, threshold, bound_radius
     of trace_rays."""
     from .curvature import bake_curvature
@@ -122,6 +135,7 @@ def render_surface(renderer, K, pose, h, w, *, which=None, aovs=('depth', 'norma
     step = n if chunk is None else int(chunk)
     want_curv = 'normal' in aovs or any(a in aovs for a in CURVATURE_AOVS)
     want_mat = any(a in aovs for a in MATERIAL_AOVS)
+    shading = tuple(a for a in aovs if a in SHADING_AOVS)
     flat = {a: torch.zeros((n, _CHANNELS[a]) if a in _CHANNELS else (n,), dtype=torch.uint8 if a == 'mask' else torch.float32, device=dev)
             for a in aovs}
     for i in range(0, n, step):
@@ -146,4 +160,11 @@ def render_surface(renderer, K, pose, h, w, *, which=None, aovs=('depth', 'norma
             for a in MATERIAL_AOVS:
                 if a in flat:
                     flat[a][dst] = mat[a].reshape(flat[a][dst].shape)
+        if shading:
+            from . import torch_glue as G
+            from .surface_shade import shade_points
+            sh = shade_points(renderer, pts, -part[idx, 3:6], which=which, terms=tuple(a for a in shading if a != 'rgb'))
+            for a in shading:
+                v = sh[a]
+                flat[a][dst] = torch.clamp(G.linear_to_srgb(v) if a in _SRGB_AOVS else v, 0.0, 1.0)
     return {a: v.reshape((h, w, 3) if a in _CHANNELS else (h, w)) for a, v in flat.items()}

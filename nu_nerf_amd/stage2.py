@@ -236,6 +236,13 @@ class Stage2Renderer(nn.Module):
         from .sdf_trace import render_surface
         return render_surface(self, K, pose, h, w, which=which, **kw)
 
+    def shade_points(self, points, view_dirs, normals=None, which='inner', **kw):
+        """The learned appearance of ONE surface at explicit points (surface_shade.py): which='inner' sdf_network_inner +
+        color_network_inner (the stage-1 form in both stage-2 models), which='outer' the stage-1 networks.  The shell's refraction is
+        not followed."""
+        from .surface_shade import shade_points
+        return shade_points(self, points, view_dirs, normals, which=which, **kw)
+
     def get_anneal_val(self, step):
         if self.cfg['anneal_end'] < 0:
             return 1.0
