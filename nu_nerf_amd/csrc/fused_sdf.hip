@@ -8,35 +8,14 @@
 // On the point sets these callers produce (8 192 rows at the reference's default batch of 512 rays) a 256 -> 256 layer is 128
 // tiles for 256 CUs and each launch is latency, not arithmetic.
 //
-// Design.  A workgroup owns a tile of 32 TMN rows (points) for ALL layers.  The activations of the tile live in LDS, k-contiguous
-// per row (stride 260 floats: ds_read_b128 fragment reads hit every 16-byte slot once per 16 rows), and ARE the A operand of every
-// layer; the weights stream through two LDS stages in 32-deep chunks exactly as in gemm_nt2_kernel (registers -> other stage in the
-// middle of a chunk, global -> registers behind it, one barrier per chunk, one memory instruction per MFMA gap) -- across layer
-// boundaries too, so the next layer's first chunk is already staged when a layer's epilogue runs.  Four waves, each 32 TMN rows x 64
-// of the 256 output columns; a layer's epilogue (bias + softplus(beta = 100)) writes the accumulators straight back over the
-// activation tile: every wave has finished reading it at the last chunk's barrier.  Layer 4's skip input [h4 (217) | embedding
-// (39)] (the 1 / sqrt 2 is folded into the packed weights) is formed by re-inserting the tile's embedding, kept in LDS.  The sdf
-// head is one wave per row with the arithmetic of skinny_fwd_kernel<1, 256>.
+// Design: the pipeline of csrc/fused_mlp.h (activation tile in LDS as the A operand of every layer, weights streamed through two LDS
+// stages behind one cursor) over the eight 256-wide layers, 32 TMN rows per workgroup.  This file's own: the embedding of the tile's
+// points (kept in LDS for layer 4's skip input [h4 (217) | embedding (39)]), the epilogue bias + softplus(beta = 100) back over the
+// activation tile, and the sdf head, one wave per row with the arithmetic of skinny_fwd_kernel<1, 256>.
 // Arithmetic order is that of the layered path (same MFMA, same k order, same softplus, same head reduction): BIT-identical
 // results, so the sampler's parity tests hold unchanged.
-// The pipeline of sdf_fused_fwd_kernel<2> below (weight cursor, MFMA schedule, epilogue, head) is repeated in sdf_jet.hip and sdf_trace.hip,
-// whose value rows must carry the bits of this kernel: a change here belongs there too (their tests compare against nu_sdf_fused_fwd).
-#include "gemm.h"
-
-#define FS_ALD 260                 // activation row stride (floats)
-#define FS_ELD 40                  // embedding row stride
-#define FS_BLD 36                  // weight-stage row stride (as NT_LDS)
-#define FS_BSTAGE (256 * FS_BLD)   // floats per weight stage: 256 output columns x 32 k (+ 4 pad)
-
-static __device__ inline float fs_embed_col(const float* x, int col) {      // get_embedder(6, 3) column (encode.hip: nu_embed_col)
-    if (col < 3) return x[col];
-    const int q = col - 3;
-    const int k = q / 6;
-    const int r = q - k * 6;
-    const int c = r >= 3 ? r - 3 : r;
-    const float a = x[c] * (float)(1 << k);
-    return r >= 3 ? cosf(a) : sinf(a);
-}
+// LDS: 32 TMN x 1 040 + 16 (activations) + 32 TMN x 160 (embedding) + 73 728 (weight stages) = 112 144 B (TMN = 1) / 150 544 B (TMN = 2).
+#include "fused_mlp.h"
 
 struct FsNet {                     // what the kernel needs of NuSdfNet (kernel-argument block)
     const float* Wp[8]; const float* bias[8];
@@ -48,38 +27,16 @@ template <int TMN>
 __global__ __launch_bounds__(256, 1) void sdf_fused_fwd_kernel(FsNet net, const float* __restrict__ X, int x_ld, int P,
                                                                float* __restrict__ sdf_out) {
     constexpr int TM = 32 * TMN;
-    __shared__ __attribute__((aligned(16))) float act[TM * FS_ALD + 4];     // (+ 4: a layer's last chunk prefetches the fragment slot behind the last row; never used)
-    __shared__ __attribute__((aligned(16))) float emb[TM * FS_ELD];
-    __shared__ __attribute__((aligned(16))) float bst[2 * FS_BSTAGE];
+    __shared__ __attribute__((aligned(16))) float act[TM * FM_ALD + FM_APAD];
+    __shared__ __attribute__((aligned(16))) float emb[TM * FM_ELD];
+    __shared__ __attribute__((aligned(16))) float bst[2 * FM_BSTAGE];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wc = tid >> 6;                                  // this wave's 64 output columns
-    const int li = lane & 31, lh = lane >> 5;
-    const int c4 = tid & 7, r0 = tid >> 3;                    // weight loader: rows r0 + 32 i (i < 8), 16-byte slot c4
-    const int a0_off = li * FS_ALD + 4 * lh, a1_off = a0_off + 32 * FS_ALD;
-    const int b0_off = (wc * 64 + li) * FS_BLD + 4 * lh, b1_off = b0_off + 32 * FS_BLD;
-    const int w_off = r0 * FS_BLD + 4 * c4;
+    const FmThread T = fm_thread();
+    const int tid = threadIdx.x, lane = T.lane, wc = T.wc, li = T.li, lh = T.lh;
+    const int a0_off = li * FM_ALD + 4 * lh, a1_off = a0_off + 32 * FM_ALD;
     const int ntiles = (P + TM - 1) / TM;
-
-    // ---- weight loader: a cursor over the chunks of all eight layers, in order (past the end it stays on the last chunk) ----
-    int ld_l = 0, ld_kt = 0;
-    const float* bp = nullptr;                                // this thread's slot of row r0 of the chunk at the cursor
-    long long bstep = 0;                                      // 32 rows further
-    f32x4 rb4[8];
-    auto set_cursor = [&]() {
-        bp = net.Wp[ld_l] + (long long)r0 * net.Kp[ld_l] + 4 * c4 + ld_kt * 32;
-        bstep = 32LL * net.Kp[ld_l];
-    };
-    auto advance = [&]() {
-        if (++ld_kt == net.Kp[ld_l] / 32) {
-            if (ld_l == 7) { --ld_kt; return; }
-            ld_kt = 0;
-            ++ld_l;
-        }
-        set_cursor();
-    };
-    struct Frag { f32x4 a0, a1, b0, b1; };
+    FmStream S;
+    FmFrag F0;
 
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int row0 = tile * TM;
@@ -89,84 +46,16 @@ __global__ __launch_bounds__(256, 1) void sdf_fused_fwd_kernel(FsNet net, const 
             int p = row0 + r;
             p = p < P ? p : P - 1;
             float x[3] = {X[(long long)p * x_ld], X[(long long)p * x_ld + 1], X[(long long)p * x_ld + 2]};
-            const float v = c < 39 ? fs_embed_col(x, c) : 0.f;
-            act[r * FS_ALD + c] = v;
-            if (c < FS_ELD) emb[r * FS_ELD + c] = v;
+            const float v = c < 39 ? fm_embed_col(x, c) : 0.f;
+            act[r * FM_ALD + c] = v;
+            if (c < FM_ELD) emb[r * FM_ELD + c] = v;
         }
-        // ---- weight pipeline prologue: chunk 0 -> stage 0, chunk 1 -> registers ----
-        ld_l = 0; ld_kt = 0;
-        set_cursor();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) rb4[i] = *reinterpret_cast<const f32x4*>(bp + i * bstep);
-        advance();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) *reinterpret_cast<f32x4*>(&bst[w_off + 32 * i * FS_BLD]) = rb4[i];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) rb4[i] = *reinterpret_cast<const f32x4*>(bp + i * bstep);
-        advance();
-        __syncthreads();
-        int cur = 0;
-        Frag F0, F1;
-        F0.b0 = *reinterpret_cast<const f32x4*>(&bst[b0_off]);
-        F0.b1 = *reinterpret_cast<const f32x4*>(&bst[b1_off]);
+        S.prologue(net, 8, bst, T);
+        S.first_b(F0, bst, T);
 
         for (int l = 0; l < 8; ++l) {
-            const int nk = net.Kp[l] / 32;
-            f32x16 acc[TMN][2];
-#pragma unroll
-            for (int i = 0; i < TMN; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-            // first A fragments of the layer (the activation tile was rewritten by the previous layer's epilogue)
-            F0.a0 = *reinterpret_cast<const f32x4*>(&act[a0_off]);
-            if (TMN == 2) F0.a1 = *reinterpret_cast<const f32x4*>(&act[a1_off]);
-#define FS_PIN __builtin_amdgcn_sched_barrier(0);
-#define FS_M(F, e, i, j) if constexpr (i < TMN) { acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(F.a##i[e], F.b##j[e], acc[i][j], 0, 0, 0); FS_PIN }
-#define FS_RA0(F, k0, kk) F.a0 = *reinterpret_cast<const f32x4*>(&act[a0_off + (k0) + (kk) * 8]); FS_PIN
-#define FS_RA1(F, k0, kk) if constexpr (TMN == 2) { F.a1 = *reinterpret_cast<const f32x4*>(&act[a1_off + (k0) + (kk) * 8]); FS_PIN }
-#define FS_RB(F, S, kk, m) F.m = *reinterpret_cast<const f32x4*>(&(S)[m##_off + (kk) * 8]); FS_PIN
-#define FS_W(i) *reinterpret_cast<f32x4*>(&so[w_off + 32 * (i) * FS_BLD]) = rb4[i]; FS_PIN
-#define FS_L(i) rb4[i] = *reinterpret_cast<const f32x4*>(bp + (i) * bstep); FS_PIN
-            const float* sc = &bst[cur * FS_BSTAGE];
-            for (int kt = 0; kt < nk; ++kt) {
-                float* so = &bst[(cur ^ 1) * FS_BSTAGE];
-                const int k0 = kt * 32;
-                // k-group 0: fragment reads of k-group 1
-                FS_M(F0, 0, 0, 0) FS_M(F0, 0, 0, 1) FS_RA0(F1, k0, 1) FS_M(F0, 0, 1, 0) FS_M(F0, 0, 1, 1)
-                FS_M(F0, 1, 0, 0) FS_M(F0, 1, 0, 1) FS_RA1(F1, k0, 1) FS_M(F0, 1, 1, 0) FS_M(F0, 1, 1, 1)
-                FS_M(F0, 2, 0, 0) FS_M(F0, 2, 0, 1) FS_RB(F1, sc, 1, b0) FS_M(F0, 2, 1, 0) FS_M(F0, 2, 1, 1)
-                FS_M(F0, 3, 0, 0) FS_M(F0, 3, 0, 1) FS_RB(F1, sc, 1, b1) FS_M(F0, 3, 1, 0) FS_M(F0, 3, 1, 1)
-                // k-group 1: the next weight chunk registers -> other stage; fragment reads of k-group 2
-                FS_M(F1, 0, 0, 0) FS_W(0) FS_M(F1, 0, 0, 1) FS_RA0(F0, k0, 2) FS_M(F1, 0, 1, 0) FS_W(1) FS_M(F1, 0, 1, 1)
-                FS_M(F1, 1, 0, 0) FS_W(2) FS_M(F1, 1, 0, 1) FS_RA1(F0, k0, 2) FS_M(F1, 1, 1, 0) FS_W(3) FS_M(F1, 1, 1, 1)
-                FS_M(F1, 2, 0, 0) FS_W(4) FS_M(F1, 2, 0, 1) FS_RB(F0, sc, 2, b0) FS_M(F1, 2, 1, 0) FS_W(5) FS_M(F1, 2, 1, 1)
-                FS_M(F1, 3, 0, 0) FS_W(6) FS_M(F1, 3, 0, 1) FS_RB(F0, sc, 2, b1) FS_M(F1, 3, 1, 0) FS_W(7) FS_M(F1, 3, 1, 1)
-                // k-group 2: the chunk after that global -> registers; fragment reads of k-group 3
-                FS_M(F0, 0, 0, 0) FS_L(0) FS_M(F0, 0, 0, 1) FS_RA0(F1, k0, 3) FS_M(F0, 0, 1, 0) FS_L(1) FS_M(F0, 0, 1, 1)
-                FS_M(F0, 1, 0, 0) FS_L(2) FS_M(F0, 1, 0, 1) FS_RA1(F1, k0, 3) FS_M(F0, 1, 1, 0) FS_L(3) FS_M(F0, 1, 1, 1)
-                FS_M(F0, 2, 0, 0) FS_L(4) FS_M(F0, 2, 0, 1) FS_RB(F1, sc, 3, b0) FS_M(F0, 2, 1, 0) FS_L(5) FS_M(F0, 2, 1, 1)
-                FS_M(F0, 3, 0, 0) FS_L(6) FS_M(F0, 3, 0, 1) FS_RB(F1, sc, 3, b1) FS_M(F0, 3, 1, 0) FS_L(7) FS_M(F0, 3, 1, 1)
-                advance();
-                __syncthreads();        // the other stage is complete; every wave holds its last fragments of this chunk
-                // k-group 3: first fragments of the next chunk (weights: the other stage, also across a layer boundary).  The activation
-                // reads are unconditional -- a branch around them would make hipcc drain the weight loads at the join -- and after a
-                // layer's last chunk they return bytes nobody uses (the next layer re-reads its first fragments behind the epilogue)
-                FS_M(F1, 0, 0, 0) FS_M(F1, 0, 0, 1) FS_RA0(F0, k0 + 32, 0) FS_M(F1, 0, 1, 0) FS_M(F1, 0, 1, 1)
-                FS_M(F1, 1, 0, 0) FS_M(F1, 1, 0, 1) FS_RA1(F0, k0 + 32, 0) FS_M(F1, 1, 1, 0) FS_M(F1, 1, 1, 1)
-                FS_M(F1, 2, 0, 0) FS_M(F1, 2, 0, 1) FS_RB(F0, so, 0, b0) FS_M(F1, 2, 1, 0) FS_M(F1, 2, 1, 1)
-                FS_M(F1, 3, 0, 0) FS_M(F1, 3, 0, 1) FS_RB(F0, so, 0, b1) FS_M(F1, 3, 1, 0) FS_M(F1, 3, 1, 1)
-                cur ^= 1;
-                sc = so;
-            }
-#undef FS_M
-#undef FS_RA0
-#undef FS_RA1
-#undef FS_RB
-#undef FS_W
-#undef FS_L
-#undef FS_PIN
+            const FmAcc<TMN> A = fm_layer<TMN>(S, net, 8, net.Kp[l] / 32, act, a0_off, a1_off, bst, F0, T);
+            const f32x16 (&acc)[TMN][2] = A.v;
             // ---- epilogue: h = softplus(acc + bias) back over the activation tile (all reads of it retired at the last barrier) ----
             const int N = net.N[l];
 #pragma unroll
@@ -179,28 +68,18 @@ __global__ __launch_bounds__(256, 1) void sdf_fused_fwd_kernel(FsNet net, const 
                     for (int r = 0; r < 16; ++r) {
                         const int row = tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                         // columns [N, 256) (layer 3: the slots of the skip embedding) are not this layer's
-                        if (col < N) act[row * FS_ALD + col] = nu_softplus100_fast(acc[tm][tn][r] + bv);
+                        if (col < N) act[row * FM_ALD + col] = nu_softplus100_fast(acc[tm][tn][r] + bv);
                     }
             }
-            if (l == 3) {               // layer 4's input: [h4 (217) | embedding (39)]
-                for (int idx = tid; idx < TM * 39; idx += 256) {
-                    const int r = idx / 39, c = idx - r * 39;
-                    act[r * FS_ALD + 217 + c] = emb[r * FS_ELD + c];
-                }
-            }
+            if (l == 3) fm_skip_reinsert(act, emb, TM);
             __syncthreads();
         }
         // ---- sdf head: one wave per row, the arithmetic of skinny_fwd_kernel<1, 256> (16 bytes per lane, xor-shuffle reduction) ----
         {
-#pragma clang fp contract(off)
             const f32x4 w = *reinterpret_cast<const f32x4*>(net.w8 + 4 * lane);
             const float b = net.b8[0];
             for (int r = wc; r < TM; r += 4) {
-                const f32x4 h = *reinterpret_cast<const f32x4*>(&act[r * FS_ALD + 4 * lane]);
-                float a = 0.f;
-                a += (h[0] * w[0] + h[1] * w[1]) + (h[2] * w[2] + h[3] * w[3]);
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+                const float a = fm_row_dot(&act[r * FM_ALD], w, lane);
                 if (lane == 0 && row0 + r < P) sdf_out[row0 + r] = a + b;
             }
         }
@@ -286,7 +165,7 @@ __global__ __launch_bounds__(256, 2) void sdf_fused16_fwd_kernel(FsNet16 net, co
             int p = row0 + r;
             p = p < P ? p : P - 1;
             float x[3] = {X[(long long)p * x_ld], X[(long long)p * x_ld + 1], X[(long long)p * x_ld + 2]};
-            const __bf16 v = (__bf16)(c < 39 ? fs_embed_col(x, c) : 0.f);
+            const __bf16 v = (__bf16)(c < 39 ? fm_embed_col(x, c) : 0.f);
             act[r * FH_ALD + c] = v;
             if (c < FH_ELD) emb[r * FH_ELD + c] = v;
         }
@@ -455,7 +334,7 @@ __global__ __launch_bounds__(512, 1) void sdf_fused16r_fwd_kernel(FsNet16 net, c
             int p = row0 + r;
             p = p < P ? p : P - 1;
             float x[3] = {X[(long long)p * x_ld], X[(long long)p * x_ld + 1], X[(long long)p * x_ld + 2]};
-            const __bf16 v = (__bf16)(c < 39 ? fs_embed_col(x, c) : 0.f);
+            const __bf16 v = (__bf16)(c < 39 ? fm_embed_col(x, c) : 0.f);
             act[r * FH_ALD + c] = v;
             if (c < FH_ELD) emb[r * FH_ELD + c] = v;
         }

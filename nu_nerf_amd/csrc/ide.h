@@ -85,9 +85,18 @@ struct NuSph {
     float pp[3];      // offset origin p'
     float t, root, snorm;
 };
-static __device__ inline NuSph nu_sph_point(const float* x, const float* dir) {
+// |x|^2 with its fused step written out, fma(x0, x0, x1 x1) + x2 x2: the shape hipcc gives the sum of nu_sph_point in the encoding kernels
+static __device__ inline float nu_sph_norm2(const float* x) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(x[0], x[0], x[1] * x[1]) + x[2] * x[2];
+}
+// n2 = |x|^2 as the caller rounds it.  Points beyond radius 0.999 are scaled by 0.999 / |x|, so rows of two kernels carry each other's
+// bits only if both round |x|^2 alike.  nu_sph_point leaves the contraction of that sum to the compiler, which chooses per kernel; a
+// kernel in which it chooses otherwise than the encoding kernels (csrc/light_bake.hip on fm_layer: fma(x2, x2, fma(x1, x1, x0 x0)))
+// passes nu_sph_norm2(x) here.
+static __device__ inline NuSph nu_sph_point_n2(const float* x, const float* dir, float n2) {
     NuSph o;
-    const float xn = sqrtf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+    const float xn = sqrtf(n2);
     const float sc = xn > 0.999f ? 0.999f / xn : 1.0f;
 #pragma unroll
     for (int c = 0; c < 3; ++c) o.pp[c] = xn > 0.999f ? x[c] / xn * 0.999f : x[c];
@@ -103,4 +112,7 @@ static __device__ inline NuSph nu_sph_point(const float* x, const float* dir) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) o.s[c] = sv[c] / o.snorm;
     return o;
+}
+static __device__ inline NuSph nu_sph_point(const float* x, const float* dir) {
+    return nu_sph_point_n2(x, dir, x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
 }

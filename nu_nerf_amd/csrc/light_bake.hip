@@ -11,7 +11,7 @@
 // layered composition for free directions (nu_spec_encode / nu_ide + three NT GEMMs + nu_skinny_fwd per predictor) writes the encoded
 // rows, three [rows, 256] hidden buffers and the ReLU sign masks of a backward nobody runs here.
 //
-// Design: the pipeline of material_bake_fwd_kernel (csrc/bake.hip).  A workgroup owns 32 rows for ALL layers of ALL predictors.  The
+// Design: the pipeline of csrc/fused_mlp.h (32-row tiles) over three input tiles.  A workgroup owns 32 rows for ALL layers of ALL predictors.  The
 // three input tiles are built in LDS first, one wave per row, lanes below 36 evaluating the IDE terms with the helpers of the encoding
 // kernels (ide.h): ol (32 x 164) = the nu_spec_encode / OLin row, il (32 x 132) = the ILin row, iw (32 x 100) = the IWin row of
 // nu_(s2_)shade_encode_fwd.  Per predictor: Kp -> 256 ReLU (from its input tile) -> 256 ReLU -> 256 ReLU (over the activation tile,
@@ -23,20 +23,16 @@
 // 163 840: one workgroup per CU.  Row strides 260 / 164 / 132 / 100 (and 36 of the weight stages) are odd multiples of 4 floats: a
 // ds_read_b128 is served in groups of 16 lanes over 64 banks, the 16 rows of a group have 16 different residues mod 16, and an odd
 // stride / 4 maps them onto the 16 different 16-byte slots of the 256-byte bank row -- no conflict, as with 260 / 292 in bake.hip.
-#include "gemm.h"
-#include "ide.h"
+#include "fused_mlp.h"
 
-#define LB_ALD 260                 // activation row stride (floats)
 #define LB_OLD 164                 // outer_light input row stride (Kp = 96 or 160)
 #define LB_ILD 132                 // inner_light input row stride (Kp = 128)
 #define LB_WLD 100                 // inner_weight input row stride (Kp = 96)
-#define LB_BLD 36                  // weight-stage row stride
-#define LB_BSTAGE (256 * LB_BLD)
-#define LB_ACT 0                   // offsets into the tile array (+ 4 each: a layer's last chunk prefetches the fragment slot behind
-#define LB_OL (32 * LB_ALD + 4)    //  the last row; never used)
-#define LB_IL (LB_OL + 32 * LB_OLD + 4)
-#define LB_IW (LB_IL + 32 * LB_ILD + 4)
-#define LB_TILE (LB_IW + 32 * LB_WLD + 4)
+#define LB_ACT 0                   // offsets into the tile array
+#define LB_OL (32 * FM_ALD + FM_APAD)
+#define LB_IL (LB_OL + 32 * LB_OLD + FM_APAD)
+#define LB_IW (LB_IL + 32 * LB_ILD + FM_APAD)
+#define LB_TILE (LB_IW + 32 * LB_WLD + FM_APAD)
 #define LB_MAXL 9                  // 3 predictors x 3 hidden layers
 #define LB_HD 8                    // raw-head record per row: direct (3), indirect (3), occlusion (1), unused (1)
 
@@ -59,39 +55,18 @@ __global__ __launch_bounds__(256, 1) void light_bake_fwd_kernel(LbNet net, int N
     constexpr int TM = 32;
     __shared__ __attribute__((aligned(16))) float tl[LB_TILE];
     __shared__ __attribute__((aligned(16))) float hd[TM * LB_HD];
-    __shared__ __attribute__((aligned(16))) float bst[2 * LB_BSTAGE];
+    __shared__ __attribute__((aligned(16))) float bst[2 * FM_BSTAGE];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wc = tid >> 6;                                  // this wave's 64 output columns
-    const int li = lane & 31, lh = lane >> 5;
-    const int c4 = tid & 7, r0 = tid >> 3;                    // weight loader: rows r0 + 32 i (i < 8), 16-byte slot c4
-    const int b0_off = (wc * 64 + li) * LB_BLD + 4 * lh, b1_off = b0_off + 32 * LB_BLD;
-    const int w_off = r0 * LB_BLD + 4 * c4;
+    const FmThread T = fm_thread();
+    const int tid = threadIdx.x, lane = T.lane, wc = T.wc, li = T.li, lh = T.lh;
     const int ntiles = (N + TM - 1) / TM;
     const int nl = net.nl;
     const int ld_ol = net.ld_ol, pe = net.pe;
     const int ld_enc = net.probe ? ld_ol + 224 : ld_ol;
     float* const act = &tl[LB_ACT];
 
-    // ---- weight loader: a cursor over the chunks of all layers, in order (past the end it stays on the last chunk) ----
-    int ld_l = 0, ld_kt = 0;
-    const float* bp = nullptr;                                // this thread's slot of row r0 of the chunk at the cursor
-    long long bstep = 0;                                      // 32 rows further
-    f32x4 rb4[8];
-    auto set_cursor = [&]() {
-        bp = net.Wp[ld_l] + (long long)r0 * net.Kp[ld_l] + 4 * c4 + ld_kt * 32;
-        bstep = 32LL * net.Kp[ld_l];
-    };
-    auto advance = [&]() {
-        if (++ld_kt == net.Kp[ld_l] / 32) {
-            if (ld_l == nl - 1) { --ld_kt; return; }
-            ld_kt = 0;
-            ++ld_l;
-        }
-        set_cursor();
-    };
-    struct Frag { f32x4 a0, b0, b1; };
+    FmStream S;
+    FmFrag F0;
 
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int row0 = tile * TM;
@@ -112,7 +87,7 @@ __global__ __launch_bounds__(256, 1) void light_bake_fwd_kernel(LbNet net, int N
                 const float att = nu_ide_att(IL, net.kinv[p]);
                 float* ol = &tl[LB_OL + r * LB_OLD];
                 if (net.sphere) {
-                    const NuSph s = nu_sph_point(x, d);
+                    const NuSph s = nu_sph_point_n2(x, d, nu_sph_norm2(x));      // (ide.h: the encoding kernels' rounding of |x|^2)
                     nu_ide_store(ol, lane, IL, td, att, 72);
                     nu_ide_store(ol + 72, lane, IL, nu_ide_dir(IL, s.s[0], s.s[1], s.s[2]), att, ld_ol - 72);
                 } else {
@@ -129,18 +104,7 @@ __global__ __launch_bounds__(256, 1) void light_bake_fwd_kernel(LbNet net, int N
                 }
             }
         }
-        // ---- weight pipeline prologue: chunk 0 -> stage 0, chunk 1 -> registers ----
-        ld_l = 0; ld_kt = 0;
-        set_cursor();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) rb4[i] = *reinterpret_cast<const f32x4*>(bp + i * bstep);
-        advance();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) *reinterpret_cast<f32x4*>(&bst[w_off + 32 * i * LB_BLD]) = rb4[i];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) rb4[i] = *reinterpret_cast<const f32x4*>(bp + i * bstep);
-        advance();
-        __syncthreads();
+        S.prologue(net, nl, bst, T);
         if (net.enc != nullptr) {           // test output: the rows as the predictors read them
             for (int idx = tid; idx < TM * ld_enc; idx += 256) {
                 const int r = idx / ld_enc, c = idx - r * ld_enc;
@@ -150,63 +114,13 @@ __global__ __launch_bounds__(256, 1) void light_bake_fwd_kernel(LbNet net, int N
                 net.enc[(long long)(row0 + r) * ld_enc + c] = v;
             }
         }
-        int cur = 0;
-        Frag F0, F1;
-        F0.b0 = *reinterpret_cast<const f32x4*>(&bst[b0_off]);
-        F0.b1 = *reinterpret_cast<const f32x4*>(&bst[b1_off]);
+        S.first_b(F0, bst, T);
 
         for (int l = 0; l < nl; ++l) {
             const int nk = net.Kp[l] / 32;
             const int a0_off = net.a_off[l] + li * net.a_ld[l] + 4 * lh;
-            f32x16 acc[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
-            // first A fragment of the layer (the activation tile was rewritten by the layer before)
-            F0.a0 = *reinterpret_cast<const f32x4*>(&tl[a0_off]);
-#define LB_PIN __builtin_amdgcn_sched_barrier(0);
-#define LB_M(F, e, j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(F.a0[e], F.b##j[e], acc[j], 0, 0, 0); LB_PIN
-#define LB_RA(F, k0, kk) F.a0 = *reinterpret_cast<const f32x4*>(&tl[a0_off + (k0) + (kk) * 8]); LB_PIN
-#define LB_RB(F, S, kk, m) F.m = *reinterpret_cast<const f32x4*>(&(S)[m##_off + (kk) * 8]); LB_PIN
-#define LB_W(i) *reinterpret_cast<f32x4*>(&so[w_off + 32 * (i) * LB_BLD]) = rb4[i]; LB_PIN
-#define LB_L(i) rb4[i] = *reinterpret_cast<const f32x4*>(bp + (i) * bstep); LB_PIN
-            const float* sc = &bst[cur * LB_BSTAGE];
-            for (int kt = 0; kt < nk; ++kt) {
-                float* so = &bst[(cur ^ 1) * LB_BSTAGE];
-                const int k0 = kt * 32;
-                // k-group 0: fragment reads of k-group 1
-                LB_M(F0, 0, 0) LB_M(F0, 0, 1) LB_RA(F1, k0, 1)
-                LB_M(F0, 1, 0) LB_M(F0, 1, 1)
-                LB_M(F0, 2, 0) LB_M(F0, 2, 1) LB_RB(F1, sc, 1, b0)
-                LB_M(F0, 3, 0) LB_M(F0, 3, 1) LB_RB(F1, sc, 1, b1)
-                // k-group 1: the next weight chunk registers -> other stage; fragment reads of k-group 2
-                LB_M(F1, 0, 0) LB_W(0) LB_M(F1, 0, 1) LB_RA(F0, k0, 2) LB_W(1)
-                LB_M(F1, 1, 0) LB_W(2) LB_M(F1, 1, 1) LB_W(3)
-                LB_M(F1, 2, 0) LB_W(4) LB_M(F1, 2, 1) LB_RB(F0, sc, 2, b0) LB_W(5)
-                LB_M(F1, 3, 0) LB_W(6) LB_M(F1, 3, 1) LB_RB(F0, sc, 2, b1) LB_W(7)
-                // k-group 2: the chunk after that global -> registers; fragment reads of k-group 3
-                LB_M(F0, 0, 0) LB_L(0) LB_M(F0, 0, 1) LB_RA(F1, k0, 3) LB_L(1)
-                LB_M(F0, 1, 0) LB_L(2) LB_M(F0, 1, 1) LB_L(3)
-                LB_M(F0, 2, 0) LB_L(4) LB_M(F0, 2, 1) LB_RB(F1, sc, 3, b0) LB_L(5)
-                LB_M(F0, 3, 0) LB_L(6) LB_M(F0, 3, 1) LB_RB(F1, sc, 3, b1) LB_L(7)
-                advance();
-                __syncthreads();        // the other stage is complete; every wave holds its last fragments of this chunk
-                // k-group 3: first fragments of the next chunk (weights: the other stage, also across a layer boundary).  The A read is
-                // unconditional and after a layer's last chunk returns bytes nobody uses (the next layer re-reads its first fragment)
-                LB_M(F1, 0, 0) LB_M(F1, 0, 1) LB_RA(F0, k0 + 32, 0)
-                LB_M(F1, 1, 0) LB_M(F1, 1, 1)
-                LB_M(F1, 2, 0) LB_M(F1, 2, 1) LB_RB(F0, so, 0, b0)
-                LB_M(F1, 3, 0) LB_M(F1, 3, 1) LB_RB(F0, so, 0, b1)
-                cur ^= 1;
-                sc = so;
-            }
-#undef LB_M
-#undef LB_RA
-#undef LB_RB
-#undef LB_W
-#undef LB_L
-#undef LB_PIN
+            const FmAcc<1> A = fm_layer<1>(S, net, nl, nk, tl, a0_off, 0, bst, F0, T);
+            const f32x16 (&acc)[2] = A.v[0];
             // ---- epilogue: bias + ReLU into the activation tile (every read of the A tile retired at the last barrier) ----
 #pragma unroll
             for (int tn = 0; tn < 2; ++tn) {
@@ -215,7 +129,7 @@ __global__ __launch_bounds__(256, 1) void light_bake_fwd_kernel(LbNet net, int N
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int row = (r & 3) + 8 * (r >> 2) + 4 * lh;
-                    act[row * LB_ALD + col] = fmaxf(acc[tn][r] + bv, 0.0f);
+                    act[row * FM_ALD + col] = fmaxf(acc[tn][r] + bv, 0.0f);
                 }
             }
             __syncthreads();
@@ -229,11 +143,7 @@ __global__ __launch_bounds__(256, 1) void light_bake_fwd_kernel(LbNet net, int N
                     const f32x4 w = *reinterpret_cast<const f32x4*>(net.Wh[pr] + j * 256 + 4 * lane);
                     const float b = net.bh[pr][j];
                     for (int r = wc; r < TM; r += 4) {
-                        const f32x4 h = *reinterpret_cast<const f32x4*>(&act[r * LB_ALD + 4 * lane]);
-                        float a = 0.f;
-                        a += (h[0] * w[0] + h[1] * w[1]) + (h[2] * w[2] + h[3] * w[3]);
-#pragma unroll
-                        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+                        const float a = fm_row_dot(&act[r * FM_ALD], w, lane);
                         if (lane == 0) hd[r * LB_HD + 3 * pr + j] = a + b;
                     }
                 }
@@ -293,7 +203,7 @@ extern "C" int nu_light_bake_fwd(const NuShadeNet* net, const float* dirs, const
             const NuLin& L = P[j];
             if (!L.Wp || !L.bias || L.N != 256 || L.Kp != (j == 0 ? Kp0 : 256)) return false;
             n.Wp[nl] = L.Wp; n.bias[nl] = L.bias; n.Kp[nl] = L.Kp;
-            n.a_off[nl] = j == 0 ? a_off : LB_ACT; n.a_ld[nl] = j == 0 ? a_ld : LB_ALD;
+            n.a_off[nl] = j == 0 ? a_off : LB_ACT; n.a_ld[nl] = j == 0 ? a_ld : FM_ALD;
             n.head[nl] = j == 2 ? pr : -1;
             ++nl;
         }

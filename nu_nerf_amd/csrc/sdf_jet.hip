@@ -5,11 +5,9 @@
 // (f = |x| - r: mean = 1 / r, gauss = 1 / r^2.)  Nothing else in the library evaluates H: the reverse sweep gives g, the training
 // backward Hessian-vector terms only.
 //
-// Design: forward-mode propagation of the jet through the pipeline of sdf_fused_fwd_kernel<2> (csrc/fused_sdf.hip).  A point carries
-// ten rows -- value, d/dx, d/dy, d/dz, d2/dxx, yy, zz, xy, xz, yz -- and a linear layer acts on all ten alike, so the hot loop is the
-// existing [rows, K] x W^T product on exact-fp32 MFMA: the activation tile (64 x 260) is the A operand of every layer, the fp32
-// packed weights (the skip's 1 / sqrt 2 folded in) stream through two 256 x 36 LDS stages behind one cursor that crosses layer
-// boundaries.  The bias goes to the value row only.
+// Design: forward-mode propagation of the jet through the pipeline of csrc/fused_mlp.h on a 64-row tile.  A point carries ten rows --
+// value, d/dx, d/dy, d/dz, d2/dxx, yy, zz, xy, xz, yz -- and a linear layer acts on all ten alike, so the hot loop is the existing
+// [rows, K] x W^T product.  The bias goes to the value row only.
 // Row order: in the accumulators of v_mfma_f32_32x32x2f32 a lane of half h = lane / 32 holds, per 32-row block, the 16 rows
 // (r & 3) + 8 (r >> 2) + 4 h.  Over the tile's two blocks that is 32 rows per lane = the 3 x 10 rows of three points (+ 2 idle), so
 // point q of half h is given exactly the rows of that lane's accumulator slots 10 q .. 10 q + 9 (slot s = 16 block + r): the
@@ -21,12 +19,8 @@
 // 256>; then one thread per point forms the curvatures.
 // The value row runs the MFMA k order, the softplus and the head of nu_sdf_fused_fwd: the sdf output carries its bits.
 // LDS: 66 576 (activations) + 10 240 (embedding jet) + 73 728 (weight stages) + 256 (head results) = 150 800 B: one workgroup per CU.
-#include "gemm.h"
+#include "fused_mlp.h"
 
-#define SJ_ALD 260                 // activation row stride (floats)
-#define SJ_ELD 40                  // embedding row stride
-#define SJ_BLD 36                  // weight-stage row stride
-#define SJ_BSTAGE (256 * SJ_BLD)
 #define SJ_PTS 6                   // points per 64-row tile
 
 // tile row of jet component j (0..9) of tile point pt (0..5): slot s = 10 q + j of the lanes of half h (pt = 3 h + q)
@@ -35,22 +29,6 @@ static __device__ inline int sj_row(int pt, int j) {
     const int s = (pt - 3 * h) * 10 + j;
     const int r = s & 15;
     return (s >> 4) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-}
-
-// jet component j of column col of get_embedder(6, 3) at x (value: the expression of fs_embed_col, fused_sdf.hip)
-static __device__ inline float sj_embed_jet(const float* x, int col, int j) {
-    if (col >= 39) return 0.f;
-    if (col < 3) return j == 0 ? x[col] : (j == 1 + col ? 1.f : 0.f);
-    const int q = col - 3;
-    const int k = q / 6;
-    const int r = q - k * 6;
-    const int c = r >= 3 ? r - 3 : r;
-    const float fk = (float)(1 << k);
-    const float a = x[c] * fk;
-    if (j == 0) return r >= 3 ? cosf(a) : sinf(a);
-    if (j == 1 + c) return r >= 3 ? -fk * sinf(a) : fk * cosf(a);
-    if (j == 4 + c) return r >= 3 ? -(fk * fk) * cosf(a) : -(fk * fk) * sinf(a);
-    return 0.f;
 }
 
 struct SjNet {                     // what the kernel needs of NuSdfNet (kernel-argument block)
@@ -62,39 +40,18 @@ struct SjOut { float *sdf, *grad, *hess, *mean, *gauss, *normal; };
 
 __global__ __launch_bounds__(256, 1) void sdf_jet_fwd_kernel(SjNet net, const float* __restrict__ X, int x_ld, int P, SjOut out) {
     constexpr int TM = 64;
-    __shared__ __attribute__((aligned(16))) float act[TM * SJ_ALD + 4];     // (+ 4: a layer's last chunk prefetches the fragment slot behind the last row; never used)
-    __shared__ __attribute__((aligned(16))) float emb[TM * SJ_ELD];
-    __shared__ __attribute__((aligned(16))) float bst[2 * SJ_BSTAGE];
+    __shared__ __attribute__((aligned(16))) float act[TM * FM_ALD + FM_APAD];
+    __shared__ __attribute__((aligned(16))) float emb[TM * FM_ELD];
+    __shared__ __attribute__((aligned(16))) float bst[2 * FM_BSTAGE];
     __shared__ float res[TM];
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wc = tid >> 6;                                  // this wave's 64 output columns
-    const int li = lane & 31, lh = lane >> 5;
-    const int c4 = tid & 7, r0 = tid >> 3;                    // weight loader: rows r0 + 32 i (i < 8), 16-byte slot c4
-    const int a0_off = li * SJ_ALD + 4 * lh, a1_off = a0_off + 32 * SJ_ALD;
-    const int b0_off = (wc * 64 + li) * SJ_BLD + 4 * lh, b1_off = b0_off + 32 * SJ_BLD;
-    const int w_off = r0 * SJ_BLD + 4 * c4;
+    const FmThread T = fm_thread();
+    const int tid = threadIdx.x, lane = T.lane, wc = T.wc, li = T.li, lh = T.lh;
+    const int a0_off = li * FM_ALD + 4 * lh, a1_off = a0_off + 32 * FM_ALD;
     const int ntiles = (P + SJ_PTS - 1) / SJ_PTS;
 
-    // ---- weight loader: a cursor over the chunks of all eight layers, in order (past the end it stays on the last chunk) ----
-    int ld_l = 0, ld_kt = 0;
-    const float* bp = nullptr;                                // this thread's slot of row r0 of the chunk at the cursor
-    long long bstep = 0;                                      // 32 rows further
-    f32x4 rb4[8];
-    auto set_cursor = [&]() {
-        bp = net.Wp[ld_l] + (long long)r0 * net.Kp[ld_l] + 4 * c4 + ld_kt * 32;
-        bstep = 32LL * net.Kp[ld_l];
-    };
-    auto advance = [&]() {
-        if (++ld_kt == net.Kp[ld_l] / 32) {
-            if (ld_l == 7) { --ld_kt; return; }
-            ld_kt = 0;
-            ++ld_l;
-        }
-        set_cursor();
-    };
-    struct Frag { f32x4 a0, a1, b0, b1; };
+    FmStream S;
+    FmFrag F0;
 
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int p0 = tile * SJ_PTS;
@@ -111,89 +68,22 @@ __global__ __launch_bounds__(256, 1) void sdf_jet_fwd_kernel(SjNet net, const fl
                 long long p = p0 + 3 * h + q;
                 p = p < P ? p : P - 1;
                 float x[3] = {X[p * x_ld], X[p * x_ld + 1], X[p * x_ld + 2]};
-                v = sj_embed_jet(x, c, j);
+                v = fm_embed_jet<2>(x, c, j);
             }
-            act[row * SJ_ALD + c] = v;
-            if (c < SJ_ELD) emb[row * SJ_ELD + c] = v;
+            act[row * FM_ALD + c] = v;
+            if (c < FM_ELD) emb[row * FM_ELD + c] = v;
         }
-        // ---- weight pipeline prologue: chunk 0 -> stage 0, chunk 1 -> registers ----
-        ld_l = 0; ld_kt = 0;
-        set_cursor();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) rb4[i] = *reinterpret_cast<const f32x4*>(bp + i * bstep);
-        advance();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) *reinterpret_cast<f32x4*>(&bst[w_off + 32 * i * SJ_BLD]) = rb4[i];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) rb4[i] = *reinterpret_cast<const f32x4*>(bp + i * bstep);
-        advance();
-        __syncthreads();
-        int cur = 0;
-        Frag F0, F1;
-        F0.b0 = *reinterpret_cast<const f32x4*>(&bst[b0_off]);
-        F0.b1 = *reinterpret_cast<const f32x4*>(&bst[b1_off]);
+        S.prologue(net, 8, bst, T);
+        S.first_b(F0, bst, T);
 
         for (int l = 0; l < 8; ++l) {
-            const int nk = net.Kp[l] / 32;
-            f32x16 acc[2][2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-            // first A fragments of the layer (the activation tile was rewritten by the previous layer's epilogue)
-            F0.a0 = *reinterpret_cast<const f32x4*>(&act[a0_off]);
-            F0.a1 = *reinterpret_cast<const f32x4*>(&act[a1_off]);
-#define SJ_PIN __builtin_amdgcn_sched_barrier(0);
-#define SJ_M(F, e, i, j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(F.a##i[e], F.b##j[e], acc[i][j], 0, 0, 0); SJ_PIN
-#define SJ_RA0(F, k0, kk) F.a0 = *reinterpret_cast<const f32x4*>(&act[a0_off + (k0) + (kk) * 8]); SJ_PIN
-#define SJ_RA1(F, k0, kk) F.a1 = *reinterpret_cast<const f32x4*>(&act[a1_off + (k0) + (kk) * 8]); SJ_PIN
-#define SJ_RB(F, S, kk, m) F.m = *reinterpret_cast<const f32x4*>(&(S)[m##_off + (kk) * 8]); SJ_PIN
-#define SJ_W(i) *reinterpret_cast<f32x4*>(&so[w_off + 32 * (i) * SJ_BLD]) = rb4[i]; SJ_PIN
-#define SJ_L(i) rb4[i] = *reinterpret_cast<const f32x4*>(bp + (i) * bstep); SJ_PIN
-            const float* sc = &bst[cur * SJ_BSTAGE];
-            for (int kt = 0; kt < nk; ++kt) {
-                float* so = &bst[(cur ^ 1) * SJ_BSTAGE];
-                const int k0 = kt * 32;
-                // k-group 0: fragment reads of k-group 1
-                SJ_M(F0, 0, 0, 0) SJ_M(F0, 0, 0, 1) SJ_RA0(F1, k0, 1) SJ_M(F0, 0, 1, 0) SJ_M(F0, 0, 1, 1)
-                SJ_M(F0, 1, 0, 0) SJ_M(F0, 1, 0, 1) SJ_RA1(F1, k0, 1) SJ_M(F0, 1, 1, 0) SJ_M(F0, 1, 1, 1)
-                SJ_M(F0, 2, 0, 0) SJ_M(F0, 2, 0, 1) SJ_RB(F1, sc, 1, b0) SJ_M(F0, 2, 1, 0) SJ_M(F0, 2, 1, 1)
-                SJ_M(F0, 3, 0, 0) SJ_M(F0, 3, 0, 1) SJ_RB(F1, sc, 1, b1) SJ_M(F0, 3, 1, 0) SJ_M(F0, 3, 1, 1)
-                // k-group 1: the next weight chunk registers -> other stage; fragment reads of k-group 2
-                SJ_M(F1, 0, 0, 0) SJ_W(0) SJ_M(F1, 0, 0, 1) SJ_RA0(F0, k0, 2) SJ_M(F1, 0, 1, 0) SJ_W(1) SJ_M(F1, 0, 1, 1)
-                SJ_M(F1, 1, 0, 0) SJ_W(2) SJ_M(F1, 1, 0, 1) SJ_RA1(F0, k0, 2) SJ_M(F1, 1, 1, 0) SJ_W(3) SJ_M(F1, 1, 1, 1)
-                SJ_M(F1, 2, 0, 0) SJ_W(4) SJ_M(F1, 2, 0, 1) SJ_RB(F0, sc, 2, b0) SJ_M(F1, 2, 1, 0) SJ_W(5) SJ_M(F1, 2, 1, 1)
-                SJ_M(F1, 3, 0, 0) SJ_W(6) SJ_M(F1, 3, 0, 1) SJ_RB(F0, sc, 2, b1) SJ_M(F1, 3, 1, 0) SJ_W(7) SJ_M(F1, 3, 1, 1)
-                // k-group 2: the chunk after that global -> registers; fragment reads of k-group 3
-                SJ_M(F0, 0, 0, 0) SJ_L(0) SJ_M(F0, 0, 0, 1) SJ_RA0(F1, k0, 3) SJ_M(F0, 0, 1, 0) SJ_L(1) SJ_M(F0, 0, 1, 1)
-                SJ_M(F0, 1, 0, 0) SJ_L(2) SJ_M(F0, 1, 0, 1) SJ_RA1(F1, k0, 3) SJ_M(F0, 1, 1, 0) SJ_L(3) SJ_M(F0, 1, 1, 1)
-                SJ_M(F0, 2, 0, 0) SJ_L(4) SJ_M(F0, 2, 0, 1) SJ_RB(F1, sc, 3, b0) SJ_M(F0, 2, 1, 0) SJ_L(5) SJ_M(F0, 2, 1, 1)
-                SJ_M(F0, 3, 0, 0) SJ_L(6) SJ_M(F0, 3, 0, 1) SJ_RB(F1, sc, 3, b1) SJ_M(F0, 3, 1, 0) SJ_L(7) SJ_M(F0, 3, 1, 1)
-                advance();
-                __syncthreads();        // the other stage is complete; every wave holds its last fragments of this chunk
-                // k-group 3: first fragments of the next chunk (weights: the other stage, also across a layer boundary).  The activation
-                // reads are unconditional and after a layer's last chunk return bytes nobody uses (the next layer re-reads them)
-                SJ_M(F1, 0, 0, 0) SJ_M(F1, 0, 0, 1) SJ_RA0(F0, k0 + 32, 0) SJ_M(F1, 0, 1, 0) SJ_M(F1, 0, 1, 1)
-                SJ_M(F1, 1, 0, 0) SJ_M(F1, 1, 0, 1) SJ_RA1(F0, k0 + 32, 0) SJ_M(F1, 1, 1, 0) SJ_M(F1, 1, 1, 1)
-                SJ_M(F1, 2, 0, 0) SJ_M(F1, 2, 0, 1) SJ_RB(F0, so, 0, b0) SJ_M(F1, 2, 1, 0) SJ_M(F1, 2, 1, 1)
-                SJ_M(F1, 3, 0, 0) SJ_M(F1, 3, 0, 1) SJ_RB(F0, so, 0, b1) SJ_M(F1, 3, 1, 0) SJ_M(F1, 3, 1, 1)
-                cur ^= 1;
-                sc = so;
-            }
-#undef SJ_M
-#undef SJ_RA0
-#undef SJ_RA1
-#undef SJ_RB
-#undef SJ_W
-#undef SJ_L
-#undef SJ_PIN
+            const FmAcc<2> A = fm_layer<2>(S, net, 8, net.Kp[l] / 32, act, a0_off, a1_off, bst, F0, T);
+            const f32x16 (&acc)[2][2] = A.v;
             // ---- epilogue: the softplus jet of each of this lane's three points, back over the activation tile (all reads of it
             //      retired at the last barrier).  Slot s = 10 q + j lives in acc[s >> 4][tn][s & 15]: static after unrolling ----
             const int N = net.N[l];
 #define SJ_A(j) acc[(q * 10 + (j)) >> 4][tn][(q * 10 + (j)) & 15]
-#define SJ_ROW(j) ((((q * 10 + (j)) >> 4) * 32 + ((q * 10 + (j)) & 3) + 8 * (((q * 10 + (j)) & 15) >> 2) + 4 * lh) * SJ_ALD)
+#define SJ_ROW(j) ((((q * 10 + (j)) >> 4) * 32 + ((q * 10 + (j)) & 3) + 8 * (((q * 10 + (j)) & 15) >> 2) + 4 * lh) * FM_ALD)
 #pragma unroll
             for (int tn = 0; tn < 2; ++tn) {
                 const int col = wc * 64 + tn * 32 + li;
@@ -223,24 +113,14 @@ __global__ __launch_bounds__(256, 1) void sdf_jet_fwd_kernel(SjNet net, const fl
             }
 #undef SJ_A
 #undef SJ_ROW
-            if (l == 3) {               // layer 4's input: [h4 (217) | embedding (39)], all ten rows of a point
-                for (int idx = tid; idx < TM * 39; idx += 256) {
-                    const int r = idx / 39, c = idx - r * 39;
-                    act[r * SJ_ALD + 217 + c] = emb[r * SJ_ELD + c];
-                }
-            }
+            if (l == 3) fm_skip_reinsert(act, emb, TM);     // all ten rows of a point
             __syncthreads();
         }
         // ---- head: the sdf row of the output layer on every row, one wave per row, the arithmetic of skinny_fwd_kernel<1, 256> ----
         {
-#pragma clang fp contract(off)
             const f32x4 w = *reinterpret_cast<const f32x4*>(net.w8 + 4 * lane);
             for (int r = wc; r < TM; r += 4) {
-                const f32x4 h = *reinterpret_cast<const f32x4*>(&act[r * SJ_ALD + 4 * lane]);
-                float a = 0.f;
-                a += (h[0] * w[0] + h[1] * w[1]) + (h[2] * w[2] + h[3] * w[3]);
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+                const float a = fm_row_dot(&act[r * FM_ALD], w, lane);
                 if (lane == 0) res[r] = a;
             }
         }

@@ -18,32 +18,17 @@
 //
 // Design.  The march is a data-dependent loop (4 .. max_iter evaluations per ray) around an eight-layer MLP.  A persistent workgroup
 // holds 64 ray SLOTS (position, direction, t, ray index, iteration count: 2.5 KB of LDS) and runs, per iteration, the whole network on the
-// 64 slot positions with the pipeline of sdf_fused_fwd_kernel<2> (csrc/fused_sdf.hip: the activation tile [64 x 260] in LDS is the A
-// operand of every layer, the fp32 packed weights stream through two [256 x 36] LDS stages behind one cursor that crosses layer
-// boundaries, exact-fp32 MFMA, the same k order, softplus and head reduction: f carries the bits of nu_sdf_fused_fwd).  After the head
+// 64 slot positions with the pipeline of csrc/fused_mlp.h and the epilogue and head of sdf_fused_fwd_kernel<2> (csrc/fused_sdf.hip): f
+// carries the bits of nu_sdf_fused_fwd.  After the head
 // wave 0 (lane = slot) applies the step, retires the rays that are done (their outputs go straight to global memory) and refills the
 // free slots from the workgroup's own ray sequence: rays b, b + G, b + 2 G, .. for workgroup b of G.  The
 // assignment is static: no global counter, no atomics, no workspace, no host read; a ray's arithmetic involves its own row of the tile
 // only, so its result does not depend on its slot, its neighbours, the grid or the ray order.  Rays that never become foreground (fg
 // 0, a non-finite origin, a miss of the bounding sphere) are retired inside the refill loop and never occupy a slot.
 // LDS: 66 576 (activations) + 10 240 (embedding) + 73 728 (weight stages) + 2 564 (slots, head results) = 153 108 B: one workgroup per CU.
-#include "gemm.h"
+#include "fused_mlp.h"
 
-#define ST_ALD 260                 // activation row stride (floats)
-#define ST_ELD 40                  // embedding row stride
-#define ST_BLD 36                  // weight-stage row stride
-#define ST_BSTAGE (256 * ST_BLD)
 #define ST_TM 64                   // ray slots per workgroup
-
-static __device__ inline float st_embed_col(const float* x, int col) {      // get_embedder(6, 3) column: the expression of fs_embed_col (fused_sdf.hip)
-    if (col < 3) return x[col];
-    const int q = col - 3;
-    const int k = q / 6;
-    const int r = q - k * 6;
-    const int c = r >= 3 ? r - 3 : r;
-    const float a = x[c] * (float)(1 << k);
-    return r >= 3 ? cosf(a) : sinf(a);
-}
 
 // One rounding per operation, never contracted.  (HIP's __fsqrt_rn is the native, not correctly rounded, square root unless the
 // library is built with OCML_BASIC_ROUNDED_OPERATIONS; sqrtf and `/` are correctly rounded under hipcc's defaults, which build.py keeps.)
@@ -87,21 +72,16 @@ static __device__ inline void st_write(const StOut& out, long long ray, float x0
 
 __global__ __launch_bounds__(256, 1) void sdf_trace_kernel(StNet net, StRays rays, StOut out) {
     constexpr int TM = ST_TM;
-    __shared__ __attribute__((aligned(16))) float act[TM * ST_ALD + 4];     // (+ 4: a layer's last chunk prefetches the fragment slot behind the last row; never used)
-    __shared__ __attribute__((aligned(16))) float emb[TM * ST_ELD];
-    __shared__ __attribute__((aligned(16))) float bst[2 * ST_BSTAGE];
+    __shared__ __attribute__((aligned(16))) float act[TM * FM_ALD + FM_APAD];
+    __shared__ __attribute__((aligned(16))) float emb[TM * FM_ELD];
+    __shared__ __attribute__((aligned(16))) float bst[2 * FM_BSTAGE];
     __shared__ float sx[TM * 3], sd[TM * 3], st[TM], res[TM];               // slot state: position, direction, t; the head's f(x)
     __shared__ int sray[TM], sit[TM];                                        // ray of the slot (-1: free), evaluations so far
     __shared__ int s_live;
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wc = tid >> 6;                                  // this wave's 64 output columns
-    const int li = lane & 31, lh = lane >> 5;
-    const int c4 = tid & 7, r0 = tid >> 3;                    // weight loader: rows r0 + 32 i (i < 8), 16-byte slot c4
-    const int a0_off = li * ST_ALD + 4 * lh, a1_off = a0_off + 32 * ST_ALD;
-    const int b0_off = (wc * 64 + li) * ST_BLD + 4 * lh, b1_off = b0_off + 32 * ST_BLD;
-    const int w_off = r0 * ST_BLD + 4 * c4;
+    const FmThread T = fm_thread();
+    const int tid = threadIdx.x, lane = T.lane, wc = T.wc, li = T.li, lh = T.lh;
+    const int a0_off = li * FM_ALD + 4 * lh, a1_off = a0_off + 32 * FM_ALD;
 
     // this workgroup's ray sequence: position q -> ray q gridDim + blockIdx, q < nq.  Neighbouring rays march alike (the rays that graze
     // the surface and run to max_iter lie along the silhouette), so they go to different workgroups; nothing is gained by keeping them
@@ -117,24 +97,8 @@ __global__ __launch_bounds__(256, 1) void sdf_trace_kernel(StNet net, StRays ray
     }
     __syncthreads();
 
-    // ---- weight loader: a cursor over the chunks of all eight layers, in order (past the end it stays on the last chunk) ----
-    int ld_l = 0, ld_kt = 0;
-    const float* bp = nullptr;                                // this thread's slot of row r0 of the chunk at the cursor
-    long long bstep = 0;                                      // 32 rows further
-    f32x4 rb4[8];
-    auto set_cursor = [&]() {
-        bp = net.Wp[ld_l] + (long long)r0 * net.Kp[ld_l] + 4 * c4 + ld_kt * 32;
-        bstep = 32LL * net.Kp[ld_l];
-    };
-    auto advance = [&]() {
-        if (++ld_kt == net.Kp[ld_l] / 32) {
-            if (ld_l == 7) { --ld_kt; return; }
-            ld_kt = 0;
-            ++ld_l;
-        }
-        set_cursor();
-    };
-    struct Frag { f32x4 a0, a1, b0, b1; };
+    FmStream S;
+    FmFrag F0;
 
     for (;;) {
         // ---- wave 0, lane = slot: the step of the slot's ray on the f(x) of the last pass, then refill of the free slots ----
@@ -208,83 +172,16 @@ __global__ __launch_bounds__(256, 1) void sdf_trace_kernel(StNet net, StRays ray
         for (int idx = tid; idx < TM * 64; idx += 256) {
             const int r = idx >> 6, c = idx & 63;
             float x[3] = {sx[3 * r], sx[3 * r + 1], sx[3 * r + 2]};
-            const float v = c < 39 ? st_embed_col(x, c) : 0.f;
-            act[r * ST_ALD + c] = v;
-            if (c < ST_ELD) emb[r * ST_ELD + c] = v;
+            const float v = c < 39 ? fm_embed_col(x, c) : 0.f;
+            act[r * FM_ALD + c] = v;
+            if (c < FM_ELD) emb[r * FM_ELD + c] = v;
         }
-        // ---- weight pipeline prologue: chunk 0 -> stage 0, chunk 1 -> registers ----
-        ld_l = 0; ld_kt = 0;
-        set_cursor();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) rb4[i] = *reinterpret_cast<const f32x4*>(bp + i * bstep);
-        advance();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) *reinterpret_cast<f32x4*>(&bst[w_off + 32 * i * ST_BLD]) = rb4[i];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) rb4[i] = *reinterpret_cast<const f32x4*>(bp + i * bstep);
-        advance();
-        __syncthreads();
-        int cur = 0;
-        Frag F0, F1;
-        F0.b0 = *reinterpret_cast<const f32x4*>(&bst[b0_off]);
-        F0.b1 = *reinterpret_cast<const f32x4*>(&bst[b1_off]);
+        S.prologue(net, 8, bst, T);
+        S.first_b(F0, bst, T);
 
         for (int l = 0; l < 8; ++l) {
-            const int nk = net.Kp[l] / 32;
-            f32x16 acc[2][2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-            // first A fragments of the layer (the activation tile was rewritten by the previous layer's epilogue)
-            F0.a0 = *reinterpret_cast<const f32x4*>(&act[a0_off]);
-            F0.a1 = *reinterpret_cast<const f32x4*>(&act[a1_off]);
-#define ST_PIN __builtin_amdgcn_sched_barrier(0);
-#define ST_M(F, e, i, j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(F.a##i[e], F.b##j[e], acc[i][j], 0, 0, 0); ST_PIN
-#define ST_RA0(F, k0, kk) F.a0 = *reinterpret_cast<const f32x4*>(&act[a0_off + (k0) + (kk) * 8]); ST_PIN
-#define ST_RA1(F, k0, kk) F.a1 = *reinterpret_cast<const f32x4*>(&act[a1_off + (k0) + (kk) * 8]); ST_PIN
-#define ST_RB(F, S, kk, m) F.m = *reinterpret_cast<const f32x4*>(&(S)[m##_off + (kk) * 8]); ST_PIN
-#define ST_W(i) *reinterpret_cast<f32x4*>(&so[w_off + 32 * (i) * ST_BLD]) = rb4[i]; ST_PIN
-#define ST_L(i) rb4[i] = *reinterpret_cast<const f32x4*>(bp + (i) * bstep); ST_PIN
-            const float* sc = &bst[cur * ST_BSTAGE];
-            for (int kt = 0; kt < nk; ++kt) {
-                float* so = &bst[(cur ^ 1) * ST_BSTAGE];
-                const int k0 = kt * 32;
-                // k-group 0: fragment reads of k-group 1
-                ST_M(F0, 0, 0, 0) ST_M(F0, 0, 0, 1) ST_RA0(F1, k0, 1) ST_M(F0, 0, 1, 0) ST_M(F0, 0, 1, 1)
-                ST_M(F0, 1, 0, 0) ST_M(F0, 1, 0, 1) ST_RA1(F1, k0, 1) ST_M(F0, 1, 1, 0) ST_M(F0, 1, 1, 1)
-                ST_M(F0, 2, 0, 0) ST_M(F0, 2, 0, 1) ST_RB(F1, sc, 1, b0) ST_M(F0, 2, 1, 0) ST_M(F0, 2, 1, 1)
-                ST_M(F0, 3, 0, 0) ST_M(F0, 3, 0, 1) ST_RB(F1, sc, 1, b1) ST_M(F0, 3, 1, 0) ST_M(F0, 3, 1, 1)
-                // k-group 1: the next weight chunk registers -> other stage; fragment reads of k-group 2
-                ST_M(F1, 0, 0, 0) ST_W(0) ST_M(F1, 0, 0, 1) ST_RA0(F0, k0, 2) ST_M(F1, 0, 1, 0) ST_W(1) ST_M(F1, 0, 1, 1)
-                ST_M(F1, 1, 0, 0) ST_W(2) ST_M(F1, 1, 0, 1) ST_RA1(F0, k0, 2) ST_M(F1, 1, 1, 0) ST_W(3) ST_M(F1, 1, 1, 1)
-                ST_M(F1, 2, 0, 0) ST_W(4) ST_M(F1, 2, 0, 1) ST_RB(F0, sc, 2, b0) ST_M(F1, 2, 1, 0) ST_W(5) ST_M(F1, 2, 1, 1)
-                ST_M(F1, 3, 0, 0) ST_W(6) ST_M(F1, 3, 0, 1) ST_RB(F0, sc, 2, b1) ST_M(F1, 3, 1, 0) ST_W(7) ST_M(F1, 3, 1, 1)
-                // k-group 2: the chunk after that global -> registers; fragment reads of k-group 3
-                ST_M(F0, 0, 0, 0) ST_L(0) ST_M(F0, 0, 0, 1) ST_RA0(F1, k0, 3) ST_M(F0, 0, 1, 0) ST_L(1) ST_M(F0, 0, 1, 1)
-                ST_M(F0, 1, 0, 0) ST_L(2) ST_M(F0, 1, 0, 1) ST_RA1(F1, k0, 3) ST_M(F0, 1, 1, 0) ST_L(3) ST_M(F0, 1, 1, 1)
-                ST_M(F0, 2, 0, 0) ST_L(4) ST_M(F0, 2, 0, 1) ST_RB(F1, sc, 3, b0) ST_M(F0, 2, 1, 0) ST_L(5) ST_M(F0, 2, 1, 1)
-                ST_M(F0, 3, 0, 0) ST_L(6) ST_M(F0, 3, 0, 1) ST_RB(F1, sc, 3, b1) ST_M(F0, 3, 1, 0) ST_L(7) ST_M(F0, 3, 1, 1)
-                advance();
-                __syncthreads();        // the other stage is complete; every wave holds its last fragments of this chunk
-                // k-group 3: first fragments of the next chunk (weights: the other stage, also across a layer boundary).  The activation
-                // reads are unconditional and after a layer's last chunk return bytes nobody uses (the next layer re-reads them)
-                ST_M(F1, 0, 0, 0) ST_M(F1, 0, 0, 1) ST_RA0(F0, k0 + 32, 0) ST_M(F1, 0, 1, 0) ST_M(F1, 0, 1, 1)
-                ST_M(F1, 1, 0, 0) ST_M(F1, 1, 0, 1) ST_RA1(F0, k0 + 32, 0) ST_M(F1, 1, 1, 0) ST_M(F1, 1, 1, 1)
-                ST_M(F1, 2, 0, 0) ST_M(F1, 2, 0, 1) ST_RB(F0, so, 0, b0) ST_M(F1, 2, 1, 0) ST_M(F1, 2, 1, 1)
-                ST_M(F1, 3, 0, 0) ST_M(F1, 3, 0, 1) ST_RB(F0, so, 0, b1) ST_M(F1, 3, 1, 0) ST_M(F1, 3, 1, 1)
-                cur ^= 1;
-                sc = so;
-            }
-#undef ST_M
-#undef ST_RA0
-#undef ST_RA1
-#undef ST_RB
-#undef ST_W
-#undef ST_L
-#undef ST_PIN
+            const FmAcc<2> A = fm_layer<2>(S, net, 8, net.Kp[l] / 32, act, a0_off, a1_off, bst, F0, T);
+            const f32x16 (&acc)[2][2] = A.v;
             // ---- epilogue: h = softplus(acc + bias) back over the activation tile (all reads of it retired at the last barrier) ----
             const int N = net.N[l];
 #pragma unroll
@@ -297,28 +194,18 @@ __global__ __launch_bounds__(256, 1) void sdf_trace_kernel(StNet net, StRays ray
                     for (int r = 0; r < 16; ++r) {
                         const int row = tm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
                         // columns [N, 256) (layer 3: the slots of the skip embedding) are not this layer's
-                        if (col < N) act[row * ST_ALD + col] = nu_softplus100_fast(acc[tm][tn][r] + bv);
+                        if (col < N) act[row * FM_ALD + col] = nu_softplus100_fast(acc[tm][tn][r] + bv);
                     }
             }
-            if (l == 3) {               // layer 4's input: [h4 (217) | embedding (39)]
-                for (int idx = tid; idx < TM * 39; idx += 256) {
-                    const int r = idx / 39, c = idx - r * 39;
-                    act[r * ST_ALD + 217 + c] = emb[r * ST_ELD + c];
-                }
-            }
+            if (l == 3) fm_skip_reinsert(act, emb, TM);
             __syncthreads();
         }
         // ---- sdf head: one wave per slot, the arithmetic of skinny_fwd_kernel<1, 256> (16 bytes per lane, xor-shuffle reduction) ----
         {
-#pragma clang fp contract(off)
             const f32x4 w = *reinterpret_cast<const f32x4*>(net.w8 + 4 * lane);
             const float b = net.b8[0];
             for (int r = wc; r < TM; r += 4) {
-                const f32x4 h = *reinterpret_cast<const f32x4*>(&act[r * ST_ALD + 4 * lane]);
-                float a = 0.f;
-                a += (h[0] * w[0] + h[1] * w[1]) + (h[2] * w[2] + h[3] * w[3]);
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+                const float a = fm_row_dot(&act[r * FM_ALD], w, lane);
                 if (lane == 0) res[r] = a + b;
             }
         }

@@ -9,7 +9,10 @@
 // GEMMs + nu_skinny_fwd each) -> nu_shade_combine_fwd, which writes every encoded row, 21 hidden buffers of [rows, 256] and the ReLU sign
 // masks of a backward nobody runs here.
 //
-// Design: the pipeline of light_bake_fwd_kernel (csrc/light_bake.hip).  A workgroup owns 32 points for ALL 21 layers of the seven
+// Design: the pipeline of csrc/fused_mlp.h over per-pass input tiles, as in light_bake_fwd_kernel (csrc/light_bake.hip) -- here still in
+// this file's own text (SS_ macros below, ss_embed_col).  On the header's fm_layer this kernel's chunk loop comes out with one
+// s_waitcnt lgkmcnt(0) where it has two in a row, and with the header's helpers alone it measured 0.1 - 0.3 % slower; it moves when that
+// is a measured change of its own (profiles/r07/README.md).  A workgroup owns 32 points for ALL 21 layers of the seven
 // predictor passes.  Per tile: one wave per point forms the geometry record (x, n^, v^, r, NoV, rho: nu_s2_dirs' arithmetic, restated)
 // in LDS.  Per pass: the pass's input tile (32 x 164, ONE region reused by all seven passes -- seven tiles at once would not fit beside the
 // activation tile and the weight stages) is built right before its first layer, one wave per row, lanes below 36 evaluating the IDE terms

@@ -235,3 +235,36 @@ def test_register_budget_of_the_surviving_hot_kernels(lib):
             assert r["lds"] <= 53 * 1024, (name, r)             # three workgroups per CU
     assert n16 == 18
 
+
+# kernel -> (object, LDS bytes its file's header states, SGPR spills: never more than before csrc/fused_mlp.h existed)
+FUSED_POINT_KERNELS = {
+    "sdf_fused_fwd_kernel<1>": ("fused_sdf", 112144, 0),
+    "sdf_fused_fwd_kernel<2>": ("fused_sdf", 150544, 0),
+    "material_bake_fwd_kernel": ("bake", 149536, 7),                # 29 with its own copy of the pipeline
+    "light_bake_fwd_kernel": ("light_bake", 158784, 37),            # 60
+    "surface_shade_fwd_kernel": ("surface_shade", 133152, 65),      # (its own copy of the pipeline)
+    "sdf_grad_fwd_kernel": ("sdf_grad", 150800, 0),
+    "sdf_jet_fwd_kernel": ("sdf_jet", 150800, 0),
+    "sdf_trace_kernel": ("sdf_trace", 153108, 4),
+}
+
+
+def test_register_budget_of_the_fused_point_kernels(lib):
+    """The fused per-point kernels (csrc/fused_mlp.h; surface_shade still carries its own copy of the pipeline): no VGPR spill, no
+    scratch, the LDS figure each file's header states (one workgroup per CU by LDS), and no more SGPR spills than recorded when the
+    header arrived, which is nowhere more than each kernel had with its own copy of the pipeline -- how the header packages the weight
+    cursor decides the SGPR allocation around the main loop, and sdf_grad, sdf_jet and the SDF forward had none."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "scripts"))
+    from kernel_regs import kernel_table
+    bdir = os.path.join(ROOT, "nu_nerf_amd", "build")
+    seen = set()
+    for kernel, (obj, lds, sgpr_spill) in FUSED_POINT_KERNELS.items():
+        for name, r in kernel_table(os.path.join(bdir, obj + ".o")):
+            if name.startswith(kernel + "("):
+                seen.add(kernel)
+                assert r["vgpr_spill"] == 0 and r["scratch"] == 0, (name, r)
+                assert r["lds"] == lds, (name, r)
+                assert r["sgpr_spill"] <= sgpr_spill, (name, r)
+    assert seen == set(FUSED_POINT_KERNELS)
+

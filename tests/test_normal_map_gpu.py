@@ -76,6 +76,8 @@ def test_row_independence_bits(gpu, parity):
     assert torch.equal(flat(bake(net, x[rolled].contiguous())), ref[rolled])
     for n in (7, 100, 1001):                                            # prefixes
         assert torch.equal(flat(bake(net, x[:n].contiguous())), ref[:n]), n
+    # more tiles than workgroups: the grid-stride tail (258 tiles of 16 points on at most 256 workgroups) repeats the points' bits
+    assert torch.equal(flat(bake(net, torch.cat([x, x[:17]]).contiguous())), torch.cat([ref, ref[:17]]))
     for i in np.linspace(0, 4095, 32).astype(int):                      # a point alone against the same point inside 4096
         assert torch.equal(flat(bake(net, x[i:i + 1].contiguous()))[0], ref[i]), i
     for pos in range(T + 1):                                            # every slot of a tile (and the next tile's first), other neighbours
