@@ -818,6 +818,33 @@ int nu_nerf_bufs_size(void);
 int nu_nerfpp_mlp_fwd(NuOpCtx* ctx, const NuNerfNet* net, const float* pt, int pt_ld, NuNerfBufs* bufs, hipStream_t stream);
 int nu_nerfpp_mlp_bwd(NuOpCtx* ctx, const NuNerfNet* net, const float* pt, int pt_ld, NuNerfBufs* bufs, const float* dsig,
                       const float* drgb, hipStream_t stream);
+/* The learned NeRF++ background of R rays as ONE fully-fused no-gradient kernel (csrc/background.hip): color_bkgr of render_core
+ * (renderer_zerothick.py:757, :777-779), the front-to-back composite of a ray's samples with every inner (|x| <= 1) alpha zero, without
+ * point records, workspace or host read.  Per ray r and sample j < S, every operation a separately rounded fp32 one unless stated:
+ *   du = d / max(|d|, 1e-12)                                        (partition_write_kernel; |d|^2 = d2 d2 + fma(d1, d1, d0 d0))
+ *   dist_j = z_{j+1} - z_j (the last section repeats its predecessor; 0 for S == 1);  mid_j = z_j + 0.5 dist_j;  x_j = o + d mid_j
+ *                                                                   (nu_sample_point of csrc/render.hip: d as given, not du)
+ *   live_j = !(sqrt((x0 x0 + x1 x1) + x2 x2) <= 1) && (t_stop == NULL || mid_j < t_stop[r])
+ *   input row: embed((x / |x|, 1 / |x|), L = 10) = 84 columns padded to 96 and embed(-du, L = 4) = 27 columns padded to 32, the
+ *              arithmetic of nerf_embed_kernel (|x|^2 = x2 x2 + fma(x1, x1, x0 x0))
+ *   layers:    eight 256-wide ReLU layers, the input row concatenated behind the hidden row at layer 5 (U5 = [h (256) | E4 (96)], K = 352);
+ *              sig = alpha_linear(h8) as nu_skinny_fwd <1, 256>;  feat = feature_linear(h8), no activation;
+ *              hv = ReLU(views_linears.0([feat | view (32)])), 288 -> 128;  raw = rgb_linear(hv) as nu_skinny_fwd <3, 128>.
+ *              Exact fp32 on v_mfma_f32_32x32x2f32 in the k order of nu_gemm_nt: the bits of nu_nerfpp_mlp_fwd (fp32 mode).
+ *   activation (nerf_act_fwd_kernel):  alpha_j = live_j ? 1 - expf(-softplus1(sig) dist_j) : 0;   c_j = srgb(expf(fminf(raw, 5)))
+ *   composite, in sample order j = 0 .. S - 1 starting from T = 1, color = 0:
+ *              color += (alpha_j T) c_j;   T *= fl(fl(1 - alpha_j) + 1e-7)        (no step fused; a sample that is not live still
+ *              multiplies T by fl(1 + 1e-7), as the reference's cumprod does);   trans = T after the last sample.
+ *   O [R, o_ld], D [R, d_ld] (the first three floats of a row; leading dimensions >= 3), z [R, S] ascending nodes, S >= 1, t_stop [R] or
+ *   NULL; color [R,3], trans [R].  Test outputs, rows in (ray, sample) order, zero on rows that are not live: enc_dbg [R S, 128] = the 96
+ *   input columns and the 32 view columns, raw_dbg [R S, 4] = sig, raw rgb, act_dbg [R S, 4] = alpha, c.  Every output pointer may be
+ *   NULL.  A ray's result does not depend on R, the ray's position, its neighbours or the grid.  Reads the fp32 packed tables (every
+ *   mlp_dtype has them) and nothing behind the 128 rows of the view layer's.
+ *   NU_ERR_ARG: net, O, D or z NULL, R < 0, S < 1, a leading dimension < 3, tables that are not the NeRF++ of NuNerfNet (pts 84 -> 256,
+ *   256 x 3, the 340-wide skip layer at index 5, 256 x 2, feat 256, alpha 1, view 283 -> 128, rgb 3).  R == 0 launches nothing. */
+int nu_background_fwd(const NuNerfNet* net, const float* O, int o_ld, const float* D, int d_ld, const float* z, int S,
+                      const float* t_stop, int R, float* color, float* trans, float* enc_dbg, float* raw_dbg, float* act_dbg,
+                      hipStream_t stream);
 
 typedef struct NuShadeNet {
     const float *WpM0, *WpTM0, *bM0; float* dWpM0;                  /* materials layer 0, 4 predictors side by side (N = 1024) */

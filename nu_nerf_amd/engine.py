@@ -800,6 +800,19 @@ class Stage1Engine:
                                       float(self.cfg.get('refrac_exp_max', self.exp_max)), L.NU_SHADE_LINEAR if linear else 0,
                                       *[addr(out.get(k)) for k in names], addr(enc), addr(raw), self.stream())
 
+    # ------------------------------------------------------------------ NeRF++ background of whole rays
+    def background(self, O, o_ld, D, d_ld, z, R, *, t_stop=None, color=None, trans=None, enc=None, raw=None, act=None):
+        """The learned NeRF++ background of R rays in ONE no-gradient kernel (csrc/background.hip; the per-ray arithmetic is stated at
+        nu_background_fwd in include/nu_nerf.h).  O, D: device addresses of [R, o_ld] / [R, d_ld] rows whose first 3 floats are origin /
+        direction; z: contiguous fp32 [R, S] ascending nodes; t_stop: fp32 [R] or None (samples whose mid-point lies at or behind it are
+        dropped).  Written to the fp32 tensors given (None: not written): color [R,3], trans [R]; enc [R S,128] / raw [R S,4] /
+        act [R S,4]: the kernel's test outputs.  No workspace, no host read.  Reads the fp32 packed tables, which pack() writes in every
+        mlp_dtype."""
+        if self._desc_dev is None or self._ptr_sig != self._signature():
+            self._upload_descs()
+        self.lib.nu_background_fwd(ctypes.byref(self._nerf_net), O, o_ld, D, d_ld, addr(z), int(z.shape[1]), addr(t_stop), R, addr(color),
+                                   addr(trans), addr(enc), addr(raw), addr(act), self.stream())
+
     # ------------------------------------------------------------------ SDF network
     def sdf_forward(self, X, x_ld, P, *, keep=True, want_feat=True):
         """SDF MLP forward on P points (X: device address of [P, x_ld] rows whose first 3 floats are x).

@@ -12,7 +12,10 @@ carries.  PNG encoding (RGBA, alpha = the mask): depth scaled to the frame's hit
 as they are, curvatures as 0.5 + k / 20 clipped.  The learned appearance (sdf_trace.SHADING_AOVS, one fused shading kernel on the hit
 pixels, surface_shade.py): `--aovs rgb` writes DIR/{k}_rgb.png as RGBA with the hit mask as alpha; the other shading images are RGB or grey
 PNGs, 0 where missed.  Only the traced surface is shaded: no background model is evaluated, no human light, and a stage-2 shell is not seen
-through.  Prints one JSON line: the output directory, the frame count and the rays hit per frame.
+through.  The learned NeRF++ background (sdf_trace.BACKGROUND_AOVS, one fused kernel on every pixel's ray, background.py): `--aovs frame`
+writes DIR/{k}_frame.png (RGB, no alpha: the shaded surface over the background it was trained with) and DIR/{k}_background.png;
+`transmittance` is a grey PNG.  --white-background / --no-white-background: what lies behind the background on missed pixels (default: the
+config's is_nerf, the reference's color + (1 - acc)).  Prints one JSON line: the output directory, the frame count and the rays hit per frame.
 """
 import argparse
 import json
@@ -23,7 +26,8 @@ DEFAULT_AOVS = ('depth', 'normal', 'mask')
 
 
 def parse_args(argv=None):
-    from .sdf_trace import ALL_AOVS as AOVS
+    from .sdf_trace import ALL_AOVS, BACKGROUND_AOVS
+    AOVS = ALL_AOVS + BACKGROUND_AOVS
     ap = argparse.ArgumentParser(prog="python -m nu_nerf_amd.render_surface", description=__doc__.split("\n\n")[1])
     ap.add_argument('--cfg', type=str, required=True, help="training config (YAML)")
     ap.add_argument('--ckpt', type=str, default=None, help="checkpoint (default data/model/{name}/model.pth; 'none': the initialised model)")
@@ -40,6 +44,9 @@ def parse_args(argv=None):
     ap.add_argument('--max_iter', type=int, default=200)
     ap.add_argument('--threshold', type=float, default=1e-5)
     ap.add_argument('--bound_radius', type=float, default=1.0)
+    ap.add_argument('--white-background', dest='white_background', action='store_true', default=None,
+                    help="frame: white behind the learned background on missed pixels (default: the config's is_nerf)")
+    ap.add_argument('--no-white-background', dest='white_background', action='store_false')
     ap.add_argument('--out', type=str, default=None, help="output directory (default data/surface/{name}-{step})")
     flags = ap.parse_args(argv)
     if flags.which is not None and not flags.stage2:
@@ -65,8 +72,10 @@ def output_dir(flags, name, step):
 
 
 def frame_paths(out, k, aovs):
-    """{aov: path} of frame k (+ 'depth.npy' when depth is asked for)."""
+    """{aov: path} of frame k (+ 'depth.npy' when depth is asked for; 'frame' also writes the background it is composed over)."""
     paths = {a: os.path.join(out, f'{k}_{a}.png') for a in aovs}
+    if 'frame' in aovs:
+        paths['background'] = os.path.join(out, f'{k}_background.png')
     if 'depth' in aovs:
         paths['depth.npy'] = os.path.join(out, f'{k}_depth.npy')
     return paths
@@ -126,7 +135,7 @@ def main(argv=None):
     from .extract_mesh import _renderer
     from .relight import write_png
     from .mask_render import _pillow
-    from .sdf_trace import SHADING_AOVS, render_surface
+    from .sdf_trace import BACKGROUND_AOVS, SHADING_AOVS, render_surface
     from .train_glue import load_checkpoint
 
     with open(flags.cfg) as fh:
@@ -147,15 +156,15 @@ def main(argv=None):
     out = output_dir(flags, cfg['name'], step)
     os.makedirs(out, exist_ok=True)
     K, poses = cameras(flags)
-    want = tuple(dict.fromkeys(flags.aovs + ('mask',)))
+    want = tuple(dict.fromkeys(flags.aovs + ('mask',) + (('background',) if 'frame' in flags.aovs else ())))
     hits = []
     for k, pose in enumerate(poses):
         imgs = render_surface(network, K, pose, flags.hw, flags.hw, which=which_of(flags), aovs=want, max_iter=flags.max_iter,
-                              threshold=flags.threshold, bound_radius=flags.bound_radius)
+                              threshold=flags.threshold, bound_radius=flags.bound_radius, white_background=flags.white_background)
         imgs = {a: v.cpu().numpy() for a, v in imgs.items()}
         paths = frame_paths(out, k, flags.aovs)
-        for a in flags.aovs:
-            if a in SHADING_AOVS and a != 'rgb':
+        for a in (p for p in paths if p != 'depth.npy'):
+            if a in BACKGROUND_AOVS or (a in SHADING_AOVS and a != 'rgb'):
                 _pillow().fromarray(to_plain(imgs[a])).save(paths[a])
             else:
                 write_png(paths[a], to_rgba(a, imgs[a], imgs['mask']))

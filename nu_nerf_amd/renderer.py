@@ -363,6 +363,12 @@ class NeROShapeRenderer(nn.Module):
         from .surface_shade import shade_points
         return shade_points(self, points, view_dirs, normals, **kw)
 
+    def render_background(self, rays_o, rays_d, **kw):
+        """The learned NeRF++ background along rays (device tensors [R, >= 3]): {'color' [R,3], 'transmittance' [R]} by one fused kernel
+        over outer_nerf (background.py)."""
+        from .background import render_background
+        return render_background(self, rays_o, rays_d, **kw)
+
     # ---- data ----------------------------------------------------------------------------------
     def _init_dataset(self):
         """Ray-batch store (renderer_zerothick.py:167-190).  `database_name: synthetic/<n_rays>` builds the seeded synthetic

@@ -13,7 +13,8 @@ trace_rays      rays -> {'pos' [R,3], 't' [R], 'sdf' [R] (the last evaluation), 
 render_surface  a pinhole camera (mask_render.pinhole_rays: K, world -> camera pose) -> images of the traced surface: mask, depth,
                 position, normal, and on request albedo / roughness / metallic (materials.bake_materials), mean / Gaussian curvature
                 (curvature.bake_curvature) and the learned appearance (SHADING_AOVS: 'rgb' and the shading terms,
-                surface_shade.shade_points), evaluated at the hit points only.
+                surface_shade.shade_points), evaluated at the hit points only; and the learned NeRF++ background of every pixel's ray
+                (BACKGROUND_AOVS: 'background', 'transmittance' and the composed 'frame', background.render_background).
 'outer' is the stage-1 SDF, 'inner' a stage-2 model's inner SDF, as in materials.py.
 """
 import torch
@@ -29,7 +30,9 @@ AOVS = GEOMETRY_AOVS + MATERIAL_AOVS + CURVATURE_AOVS
 SHADING_AOVS = ('rgb', 'diffuse_color', 'specular_color', 'diffuse_light', 'specular_light', 'occ_prob', 'indirect_light',
                 'refraction_light', 'reflection_weight')
 ALL_AOVS = AOVS + SHADING_AOVS
-_CHANNELS = {'position': 3, 'normal': 3, 'albedo': 3, 'rgb': 3, 'diffuse_color': 3, 'specular_color': 3, 'diffuse_light': 3,
+# the learned NeRF++ background of every pixel's ray (background.py) and the frame composed of it and 'rgb'
+BACKGROUND_AOVS = ('background', 'transmittance', 'frame')
+_CHANNELS = {'background': 3, 'frame': 3, 'position': 3, 'normal': 3, 'albedo': 3, 'rgb': 3, 'diffuse_color': 3, 'specular_color': 3, 'diffuse_light': 3,
              'specular_light': 3, 'indirect_light': 3, 'refraction_light': 3}
 _SRGB_AOVS = ('diffuse_light', 'specular_light')       # the kernel returns these two linear; their pictures are clamp(linear_to_srgb(.))
 
@@ -94,14 +97,15 @@ def trace_rays(renderer, rays_o, rays_d, *, which=None, mask=None, max_iter=200,
 
 def _check_aovs(aovs):
     aovs = (aovs,) if isinstance(aovs, str) else tuple(aovs)
-    bad = [a for a in aovs if a not in ALL_AOVS]
+    bad = [a for a in aovs if a not in ALL_AOVS + BACKGROUND_AOVS]
     if bad or not aovs:
-        raise ValueError(f"aovs={aovs!r}: expected one or more of {ALL_AOVS}")
+        raise ValueError(f"aovs={aovs!r}: expected one or more of {ALL_AOVS + BACKGROUND_AOVS}")
     return aovs
 
 
 @torch.no_grad()
-def render_surface(renderer, K, pose, h, w, *, which=None, aovs=('depth', 'normal', 'mask'), chunk=None, **trace_kw):
+def render_surface(renderer, K, pose, h, w, *, which=None, aovs=('depth', 'normal', 'mask'), chunk=None, white_background=None,
+                   **trace_kw):
     """Images of the SDF's surface from one pinhole camera (K [3,3], pose [3,4] world -> camera, pixel centres, unit directions: the rays
     of mask_render.pinhole_rays): one trace (entry_forward=True: a camera inside the bounding sphere looks forward), then the jet and the
     material bake at the hit points only.  -> dict of device tensors, one per name in `aovs`:
@@ -112,7 +116,12 @@ def render_surface(renderer, K, pose, h, w, *, which=None, aovs=('depth', 'norma
       'rgb' [h,w,3]      'diffuse_color', 'specular_color', 'indirect_light', 'refraction_light' [h,w,3]
       'diffuse_light', 'specular_light' [h,w,3] (sRGB of the diffuse query's light / of the roughness-0 specular light)
       'occ_prob', 'reflection_weight' [h,w]
-    Only this one surface is shaded: no human light, no background model, no refraction through a stage-2 shell.
+    and the learned NeRF++ background (BACKGROUND_AOVS; background.render_background on EVERY pixel's ray at background.default_nodes,
+    stopped at the hit's t on hit pixels, one fused kernel per pass):
+      'background' [h,w,3] (the composite of the outer samples in front of the surface)      'transmittance' [h,w] (what they let through)
+      'frame' [h,w,3] = clamp(background + transmittance rgb, 0, 1) on hit pixels, clamp(background + (white ? transmittance : 0), 0, 1)
+              on missed ones; white_background: None = cfg['is_nerf'] (the reference's color + (1 - acc) of NeRF-synthetic data)
+    Only this one surface is shaded: no human light, no refraction through a stage-2 shell; the surface is opaque to the background.
     chunk: rays per pass (None: the whole image at once); the result does not depend on it.  trace_kw: max_iter, threshold, bound_radius
     of trace_rays."""
     from .curvature import bake_curvature
@@ -136,6 +145,8 @@ def render_surface(renderer, K, pose, h, w, *, which=None, aovs=('depth', 'norma
     want_curv = 'normal' in aovs or any(a in aovs for a in CURVATURE_AOVS)
     want_mat = any(a in aovs for a in MATERIAL_AOVS)
     shading = tuple(a for a in aovs if a in SHADING_AOVS)
+    want_bg = any(a in aovs for a in BACKGROUND_AOVS)
+    white = bool(renderer.cfg.get('is_nerf', False)) if white_background is None else bool(white_background)
     flat = {a: torch.zeros((n, _CHANNELS[a]) if a in _CHANNELS else (n,), dtype=torch.uint8 if a == 'mask' else torch.float32, device=dev)
             for a in aovs}
     for i in range(0, n, step):
@@ -160,11 +171,23 @@ def render_surface(renderer, K, pose, h, w, *, which=None, aovs=('depth', 'norma
             for a in MATERIAL_AOVS:
                 if a in flat:
                     flat[a][dst] = mat[a].reshape(flat[a][dst].shape)
-        if shading:
+        if shading or 'frame' in aovs:
             from . import torch_glue as G
             from .surface_shade import shade_points
             sh = shade_points(renderer, pts, -part[idx, 3:6], which=which, terms=tuple(a for a in shading if a != 'rgb'))
             for a in shading:
                 v = sh[a]
                 flat[a][dst] = torch.clamp(G.linear_to_srgb(v) if a in _SRGB_AOVS else v, 0.0, 1.0)
+        if want_bg:
+            from .background import render_background
+            t_stop = torch.where(tr['hit'] != 0, tr['t'], torch.full_like(tr['t'], float('inf')))
+            bg = render_background(renderer, part[:, :3], part[:, 3:], t_stop=t_stop)
+            if 'background' in flat:
+                flat['background'][i:i + step] = bg['color']
+            if 'transmittance' in flat:
+                flat['transmittance'][i:i + step] = bg['transmittance']
+            if 'frame' in flat:
+                behind = bg['transmittance'][:, None].repeat(1, 3) if white else torch.zeros_like(bg['color'])
+                behind[idx] = bg['transmittance'][idx][:, None] * torch.clamp(sh['rgb'], 0.0, 1.0)
+                flat['frame'][i:i + step] = torch.clamp(bg['color'] + behind, 0.0, 1.0)
     return {a: v.reshape((h, w, 3) if a in _CHANNELS else (h, w)) for a, v in flat.items()}

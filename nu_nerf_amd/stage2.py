@@ -243,6 +243,12 @@ class Stage2Renderer(nn.Module):
         from .surface_shade import shade_points
         return shade_points(self, points, view_dirs, normals, which=which, **kw)
 
+    def render_background(self, rays_o, rays_d, **kw):
+        """The learned NeRF++ background along rays (background.py): the outer_nerf of the stage-1 network the model carries -- the inner
+        engine never has one."""
+        from .background import render_background
+        return render_background(self, rays_o, rays_d, **kw)
+
     def get_anneal_val(self, step):
         if self.cfg['anneal_end'] < 0:
             return 1.0
