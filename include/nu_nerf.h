@@ -1103,6 +1103,46 @@ int nu_grid_scatter(const float* X, const float* Y, const float* Z, int nx, int 
                     const void* workspace, long long workspace_bytes, const float* val, float outside_val, float* u, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Block-sparse mesh extraction (csrc/mcubes_sparse.hip): the same lattice (X[i], Y[j], Z[k]), cut into point-blocks of
+ * block^3 points (block = 4 or 8; block (bi, bj, bk) owns [block bi, block bi + block) per axis, id = (bi nby + bj) nbz + bk, int32,
+ * nb* = ceil(n* / block)).  slot [nbx nby nbz] int32: -1 = inactive, else the block's slot (ascending block id); blocks [nslots] int32:
+ * block id of every slot; u [nslots][block^3] fp32, in-block C order (rows r = slot block^3 + t, 64-bit).
+ *   nu_smc_regions          per block, from its REGION (the lattice box [block b - 1, block b + block] clipped to the grid): flags
+ *                           [nblk] int32 (0 = no point can lie in the unit ball, 1 = wholly inside, 2 = rim), probe [nblk,3] (the
+ *                           region's centre, pulled radially to |p| = 0.999 when farther out), radius [nblk] (half diagonal +
+ *                           |centre - probe|, times 1 + 1e-6).  Computed in double, stored in fp32; zero where flags is 0
+ *   nu_smc_activate         active[probe_blocks[i]] = the rule for the level set at iso on the probe values f[i] (and g[i], or NULL); with
+ *                           f' = f - iso: interior |f'| <= L r, rim f' <= L r (needs outside_val > iso); composite (g where f < 0, 1
+ *                           elsewhere; iso < 1), with g' = g - iso: f <= L r and (|g'| <= L r [rim: g' <= L r] or (|f| <= L r and
+ *                           g' <= L r)); L = +inf activates every probed block.  L r is one fp32 product; a NaN value activates
+ *   nu_smc_block_rows       x rows [n,3] of the block points r0 .. r0 + n (indices beyond the grid clamped)
+ *   nu_smc_finish           u[r] = outside_val at the points that fail the inside test of nu_grid_compact (and at the padding)
+ *   nu_smc_count / _scan / _write_vertices / _write_triangles    marching cubes on the block list, the conventions of nu_mc_*: a cell
+ *                           belongs to the block of its min corner and is processed iff its eight corners lie in active blocks; an
+ *                           owned edge gives a vertex iff both ends are active and straddle.  V is ordered by (slot, in-block point,
+ *                           axis), F by (slot, in-block cell, table slot); first_vid [nslots block^3] int32.  totals[3] (device,
+ *                           int64) = (Nv, Nf, open edges): owned straddling edges with an in-grid incident cell that is not processed
+ *                           -- 0 unless the active band cut the surface.  The workspace (nu_smc_workspace_bytes, 8-byte aligned)
+ *                           carries counts and offsets from one call to the next.
+ * --------------------------------------------------------------------------------------------------------- */
+long long nu_smc_workspace_bytes(int nslots);
+int nu_smc_regions(const float* X, const float* Y, const float* Z, int nx, int ny, int nz, int block, int* flags, float* probe,
+                   float* radius, hipStream_t stream);
+int nu_smc_activate(const int* flags, const float* radius, const int* probe_blocks, int nprobe, const float* f, const float* g,
+                    float lipschitz, float iso, int* active, hipStream_t stream);
+int nu_smc_block_rows(const float* X, const float* Y, const float* Z, int nx, int ny, int nz, int block, const int* blocks, int nslots,
+                      long long r0, long long n, float* rows, hipStream_t stream);
+int nu_smc_finish(const float* X, const float* Y, const float* Z, int nx, int ny, int nz, int block, const int* blocks, int nslots,
+                  float outside_val, float* u, hipStream_t stream);
+int nu_smc_count(const float* u, const int* slot, const int* blocks, int nslots, int nx, int ny, int nz, int block, float iso,
+                 void* workspace, long long workspace_bytes, hipStream_t stream);
+int nu_smc_scan(int nslots, void* workspace, long long workspace_bytes, long long* totals, hipStream_t stream);
+int nu_smc_write_vertices(const float* u, const int* slot, const int* blocks, int nslots, int nx, int ny, int nz, int block, float iso,
+                          const void* workspace, long long workspace_bytes, float* V, int* first_vid, hipStream_t stream);
+int nu_smc_write_triangles(const float* u, const int* slot, const int* blocks, int nslots, int nx, int ny, int nz, int block, float iso,
+                           const void* workspace, long long workspace_bytes, const int* first_vid, int* F, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Isotropic remeshing (extract_mesh_stage1.py:44-50: pymeshlab meshing_isotropic_explicit_remeshing; Botsch & Kobbelt 2004), one
  * pass per entry; the driver (nu_nerf_amd/remesh.py) sorts and scans between them.  V fp32 [nv,3], F int32 [nf,3] (a dead face is
  * (-1,-1,-1)), half-edge h = 3 f + s from F[f][s] to F[f][(s+1)%3], nh = 3 nf.  Every buffer is the caller's and sized by these

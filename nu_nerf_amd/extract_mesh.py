@@ -1,5 +1,5 @@
 """python -m nu_nerf_amd.extract_mesh --cfg CFG [--resolution 1024] [--ckpt PATH] [--out PATH] [--stage2] [--remesh] [--fix ...]
-[--decimate N]
+[--decimate N] [--sparse [--block 8] [--lipschitz 2.0]]
 
 extract_mesh_stage1.py on the GPU: the renderer named by the config (`zero_thickness` picks the module set) loads
 data/model/{name}/model.pth (train_glue.save_checkpoint format), its SDF is sampled on the [-1,1]^3 grid (mesh.sdf_grid), marching
@@ -14,6 +14,11 @@ remeshes the fixed mesh instead of the raw one.  Without --fix every file is wri
 
 --stage2: extract_mesh_stage2.py -- a stage-2 checkpoint; the field is the inner sdf where the stage-1 sdf is < 0 and 1 elsewhere
 (mesh.stage2_inner_grid), no face flip.
+
+--sparse: the same mesh through the block-sparse path (mesh.extract_mesh_sparse / extract_stage2_mesh_sparse): the SDF is
+evaluated only in the blocks of --block^3 grid points (4 or 8) that the zero set can reach under the gradient bound --lipschitz; if
+the kept blocks turn out to cut the surface the bound is doubled and the extraction repeated.  The vertices and triangles are those
+of the dense path, ordered by block.  --fix, --decimate and --remesh follow unchanged; without --sparse nothing changes.
 """
 import argparse
 import os
@@ -32,9 +37,18 @@ def parse_args(argv=None):
     ap.add_argument('--fix', action='store_true', help="also write OUT_fixed.ply without floaters; --remesh then starts from it")
     ap.add_argument('--decimate', type=int, default=None, metavar='N',
                     help="also write OUT_decimated.ply with about N faces (after --fix); --remesh then starts from it")
+    ap.add_argument('--sparse', action='store_true', help="evaluate the SDF only in the blocks near the surface (same mesh, ordered by block)")
+    ap.add_argument('--block', type=int, default=None, choices=(4, 8), help="--sparse: grid points per block edge (default 8)")
+    ap.add_argument('--lipschitz', type=float, default=None, help="--sparse: bound on |grad sdf| used to cull blocks (default 2.0)")
     from .clean_mesh import add_fix_options
     add_fix_options(ap)
     flags = ap.parse_args(argv)
+    if not flags.sparse and (flags.block is not None or flags.lipschitz is not None):
+        ap.error("--block and --lipschitz belong to --sparse")
+    flags.block = 8 if flags.block is None else flags.block
+    flags.lipschitz = 2.0 if flags.lipschitz is None else flags.lipschitz
+    if not flags.lipschitz > 0:
+        ap.error("--lipschitz must be positive")
     if flags.decimate is not None and flags.decimate < 4:
         ap.error("--decimate must be >= 4")
     return flags
@@ -68,11 +82,23 @@ def main(argv=None):
         s1_ckpt = network.cfg.get('stage1_ckpt_dir')
         if s1_ckpt and os.path.exists(s1_ckpt):                # extract_mesh_stage2.py:27-34: stage 1 from its own checkpoint
             load_checkpoint(s1_ckpt, network.stage1_network, map_location='cpu')
-        u = mesh.stage2_inner_grid(network, res, slab_points=flags.slab_points)
-        V, F = mesh.marching_cubes(u, 0.0)
-        V, F = mesh._to_world(V, res, mesh.BOX_MIN, mesh.BOX_MAX), F.cpu().numpy()
+        if flags.sparse:
+            stats = {}
+            V, F = mesh.extract_stage2_mesh_sparse(network, res, 0.0, block=flags.block, lipschitz=flags.lipschitz,
+                                                   slab_points=flags.slab_points, stats=stats)
+            print(f'sparse: {stats}')
+        else:
+            u = mesh.stage2_inner_grid(network, res, slab_points=flags.slab_points)
+            V, F = mesh.marching_cubes(u, 0.0)
+            V, F = mesh._to_world(V, res, mesh.BOX_MIN, mesh.BOX_MAX), F.cpu().numpy()
     else:
-        V, F = mesh.extract_mesh(network, res, 0.0, slab_points=flags.slab_points)
+        if flags.sparse:
+            stats = {}
+            V, F = mesh.extract_mesh_sparse(network, res, 0.0, block=flags.block, lipschitz=flags.lipschitz,
+                                            slab_points=flags.slab_points, stats=stats)
+            print(f'sparse: {stats}')
+        else:
+            V, F = mesh.extract_mesh(network, res, 0.0, slab_points=flags.slab_points)
         F = np.ascontiguousarray(np.fliplr(F))
     out = flags.out or os.path.join('data', 'meshes', f'{cfg["name"]}-{step}.ply')
     os.makedirs(os.path.dirname(out) or '.', exist_ok=True)

@@ -14,6 +14,8 @@ run PyMCubes on a host grid: network/field.py:1286-1317).
   decimate          quadric-error edge-collapse decimation to a face budget (decimate.py, csrc/decimate.hip)
   connected_components / component_stats / remove_floaters   component labelling, statistics and floater removal (components.py,
                     csrc/components.hip)
+  SparseGrid / sparse_sdf_grid / marching_cubes_sparse / extract_mesh_sparse / stage2_inner_sparse   block-sparse extraction: the SDF
+                    evaluated only near the surface (mesh_sparse.py, csrc/mcubes_sparse.hip)
 
 Conventions (DESIGN.md "Mesh extraction"): a grid point is INSIDE when u < threshold; triangles wind so that their right-handed
 normal points inside, which is where the reference's raw PyMCubes output of an sdf (positive outside) points before the face flip of
@@ -435,3 +437,15 @@ def remove_floaters(V, F, keep=1, min_area_frac=None, min_faces=None, drop_cavit
     from .components import remove_floaters as _remove
     return _remove(V, F, keep=keep, min_area_frac=min_area_frac, min_faces=min_faces, drop_cavities=drop_cavities,
                    connectivity=connectivity, stats=stats)
+
+
+# block-sparse extraction (mesh_sparse.py, csrc/mcubes_sparse.hip): re-exported here, loaded on first use (mesh_sparse imports this module)
+_SPARSE = ('SparseGrid', 'sparse_sdf_grid', 'marching_cubes_sparse', 'extract_mesh_sparse', 'stage2_inner_sparse',
+           'extract_stage2_mesh_sparse')
+
+
+def __getattr__(name):
+    if name in _SPARSE:
+        from . import mesh_sparse
+        return getattr(mesh_sparse, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
